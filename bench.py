@@ -16,11 +16,22 @@ N>1 also trains the SHARED background model (train.py:308-316) ray-sharded over 
 one real collective (ONE all-reduce of [gradients | loss terms] per step over RCCL) - and reports it under `with_background`;
 `value` stays the objects-only rate (the metric).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, pre-heats and warms up, times exactly --steps steps once and prints ONE JSON line (rank 0) with the contract
+fields: metric, value, unit, higher_is_better, dtype, ms_per_step (+ the run's configuration).  --full adds everything else the
+benchmark measures, each in runs of its own after the timed region (the timed region is then repeated --repeats times, default 5,
+and the median reported):
   roofline     - the dominant kernel against the matrix peaks (fp32-equivalent and the executed bf16 pipe), timed live with the
-                 dispatch's own begin / end events
-  cpu_baseline - the reference's own step (oracle/_ref) timed on this host's cores (reported, not a target)
+                 dispatch's own begin / end events; HBM traffic observed by two rocprofv3 --pmc passes
+  cpu_baseline / gpu_reference_baseline / gpu_eager_baseline - the reference's own step (oracle/_ref) on this host's cores and on
+                 this GPU, and the eager ATen port (reported, not a target)
   value_fp32_equivalent_backward / value_exact_fp32_kernel / precision - the precision / throughput curve of the hidden-32 kernels
+  other_configs / frame - the other BASELINE configurations and a whole mapping frame (N = 1)
+  with_background / world.region_costs - the shared background model beside the objects and the region's collectives (N > 1)
+
+--dump-outputs DIR writes what the timed path hands its caller after its last timed step - that step's loss and empty-mask
+flags and the 15 trained parameter tensors of rank 0's objects - as DIR/<name>.npy (float32).  Inputs and initial parameters
+come from fixed seeds and the pre-heat's training is undone before the warm-up, so the same arguments give the same inputs and
+the same number of training steps in every run: two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -157,6 +168,27 @@ def gpu_eager_baseline(cfg, dev, budget_s=1.5):
     return {"value": rays * n / el, "unit": "rays/s", "kind": "port", "ms_per_step": el / n * 1e3,
             "sample": f"{n} eager steps (fwd+loss+bwd+torch.optim.AdamW) of the same workload on {torch.cuda.get_device_name(dev)}, "
                       f"torch {torch.__version__}"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, res, k, tfc, tB):
+    """--dump-outputs: what the timed path's caller holds after its last step, as float32 .npy files under ``dirname``: that step's
+    loss (``loss`` [1]) and empty-mask switches (``flags`` [4]: drop_depth, drop_colour, drop_opacity, explode), and the trained
+    parameters updated in place (``fc00_in_layer_0_weight`` .. ``fc13_out_color_bias`` [n, ...] in layout.FC_NAMES order,
+    ``pe_B_layer_weight`` [n, 21, 3])."""
+    arrays = {"loss": res.loss[k - 1:k], "flags": res.flags[k - 1].float()}
+    for t, name in enumerate(layout.FC_NAMES):
+        arrays[f"fc{t:02d}_{name.replace('.', '_')}"] = tfc[t]
+    arrays["pe_B_layer_weight"] = tB
+    arrays = {name: a.detach().cpu().numpy().astype(np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def library_sha256():
@@ -535,11 +567,12 @@ def summarise(out):
 
 
 def emit(out):
-    try:
-        out.pop("summary", None)
-        out["summary"] = summarise(out)             # last key of the line
-    except Exception as e:
-        out["summary"] = {"error": f"{type(e).__name__}: {e}"}
+    if out.get("full"):                             # a plain line holds only the contract fields: nothing to summarise
+        try:
+            out.pop("summary", None)
+            out["summary"] = summarise(out)         # last key of the line
+        except Exception as e:
+            out["summary"] = {"error": f"{type(e).__name__}: {e}"}
     # RCCL writes its banner through C stdio (buffered when stdout is a file): push it out first, the JSON line stays last
     try:
         import ctypes
@@ -642,7 +675,7 @@ def main():
     ap.add_argument("--with-background", action="store_true")      # also train the SHARED background model (train.py:308-316; hidden 128,
                                                                      # 1200 rays / step split over the ranks, ONE gradient all-reduce per
                                                                      # step) next to the objects, on a second stream; reported separately.
-                                                                     # ON by default whenever WORLD_SIZE > 1 (the scaling run exercises RCCL)
+                                                                     # ON by default with --full whenever WORLD_SIZE > 1 (the scaling run exercises RCCL)
     ap.add_argument("--no-background", action="store_true")
     ap.add_argument("--pmc-file", default=None)                      # roofline.traffic from THIS file (tests/tools/pmc_summary.py output of the
                                                                      # FETCH_SIZE / WRITE_SIZE passes tests/tools/gpu_bench_with_pmc.sh ran just before,
@@ -653,8 +686,12 @@ def main():
     ap.add_argument("--timed-only", action="store_true")            # skip the roofline / baseline legs (for kernel traces of the timed region)
     ap.add_argument("--unbound", action="store_true")               # marshal the arguments on every frame call (VmapStep.train_steps)
     ap.add_argument("--graph", action="store_true")                 # measurement: the bound frame call replayed as a hipGraph (bit-identical; no gain: profiles/r03i)
-    ap.add_argument("--repeats", type=int, default=5)               # the timed region (EXACTLY --steps steps between barrier + synchronize) is measured this many
+    ap.add_argument("--repeats", type=int, default=None)            # the timed region (EXACTLY --steps steps between barrier + synchronize) is measured this many
                                                                      # times back to back; ms_per_step / value = the MEDIAN, min / max / all reported
+                                                                     # (default: 1 in a plain run, 5 with --full)
+    ap.add_argument("--full", action="store_true")                  # also run every leg beside the headline figure (roofline, baselines, precision,
+                                                                     # other configurations, frame, background, collectives): see the module docstring
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)   # write the timed path's outputs after its last timed step as DIR/<name>.npy
     ap.add_argument("--no-other-configs", action="store_true")      # skip the `other_configs` legs (configs[0], [3], [4] and the background step)
     ap.add_argument("--no-precision", action="store_true")          # skip the `precision` leg (measured errors of the two hidden-32 kernels)
     ap.add_argument("--pmc-timeout", type=float, default=60.0)      # per rocprofv3 --pmc pass of the traffic observation (it runs LAST, under a watchdog)
@@ -662,6 +699,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit(f"bench.py: --gpus {args.gpus}")
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps}")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: no launcher set the rank environment up, so this process becomes the launcher
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -724,15 +765,19 @@ def main():
     # driver.HipMapper does for its slab and its sampler's frame buffers
     bound = None if args.unbound else op.bind(tfc, tB, tsc, *fargs, opt=opt, flag_reduce=flag_reduce, graph=args.graph)
 
+    last = {}                                  # the last frame call's result and step count (--dump-outputs)
+
     def run(n_steps):
         done = 0
         while done < n_steps:
             k = min(ipf, n_steps - done)
             if bound is not None:
-                bound.train_steps(k)
+                res = bound.train_steps(k)
             else:
-                op.train_steps(tfc, tB, tsc, *fargs, opt=opt, n_steps=k, flag_reduce=flag_reduce)
+                res = op.train_steps(tfc, tB, tsc, *fargs, opt=opt, n_steps=k, flag_reduce=flag_reduce)
             done += k
+        if n_steps > 0:
+            last["res"], last["k"] = res, k
 
     def barrier():
         if dist:
@@ -745,6 +790,12 @@ def main():
         # ~preheat_ms so that the clocks / power state are those of a running mapper rather than of an idle chip.
         # With several ranks every frame call contains a collective (the flag reduction), so the NUMBER of pre-heat frames must
         # be the same on every rank: it is fixed from a timed probe (MAX over ranks), not by each rank's own clock.
+        # The number of pre-heat frames follows the clock, so the training it does is undone afterwards: the warm-up and the timed
+        # region start from the seeded parameters and a fresh optimiser, whatever the pre-heat took (--dump-outputs compares runs).
+        state = [t.clone() for t in tfc] + [tB.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()]
+        if opt.step_counter is not None:                # --graph: the optimiser's step count lives on the device
+            state.append(opt.step_counter.clone())
+        step0 = opt.step
         run(ipf)
         torch.cuda.synchronize()
         t_ph = time.perf_counter()
@@ -758,6 +809,11 @@ def main():
         frames = min(frames, 4000)
         for _ in range(frames):
             run(ipf)
+        # in place: the bound frame holds these tensors' addresses
+        live = list(tfc) + [tB, opt.exp_avg, opt.exp_avg_sq] + ([opt.step_counter] if opt.step_counter is not None else [])
+        for dst, src in zip(live, state):
+            dst.copy_(src)
+        opt.step = step0
         torch.cuda.synchronize()
         preheat_steps = (frames + 2) * ipf
     run(args.warmup)
@@ -783,10 +839,13 @@ def main():
         td.all_reduce(t, op=td.ReduceOp.MAX)
         t = [float(x) for x in t.tolist()]
         times, times_b = t[:len(own_times)], t[len(own_times):]
+    if args.dump_outputs and rank == 0:
+        # before anything else trains these parameters further
+        dump_outputs(args.dump_outputs, last["res"], last["k"], tfc, tB)
     # N > 1: what the region's collectives cost on their own, and the same measurement over TEN frame calls per repeat (a barrier is
     # then < 1 % of the region): reported beside `value`, which stays EXACTLY --steps steps per the contract
     region = None
-    if dist:
+    if dist and args.full:
         region = multi_rank_region_costs(td, dev, run, barrier, ipf, n * R * world,
                                          flags=torch.zeros(ipf, 4, dtype=torch.int32, device=dev), reduce_flags=flag_reduce)
     elapsed = _median(times)
@@ -842,18 +901,6 @@ def main():
                 raise SystemExit(f"bench.py --gpus {world}: backend {td.get_backend()} / RCCL version {rccl_version}")
     out = None
     if rank == 0:
-        # ---- dominant kernel, timed live on the launch stream ----
-        # (event pairs around every launch of the dominant kernel inside the real prep / main / finalize sequence; `frac`
-        # uses the RAW pair time, which is what a rocprofv3 --kernel-trace of the same command reports per dispatch
-        # (profiles/); the time minus the cost of an empty event pair and back-to-back launches of the kernel alone are
-        # reported next to it)
-        b0 = tuple(x[:, :R] for x in fargs)
-        k_ms_alone = op.profile_main_kernel(tfc, tB, tsc, *b0, reps=args.profile_reps)
-        reps = max(1, args.profile_reps // ipf)
-        pairs = [op.profile_train_steps(tfc, tB, tsc, *fargs, opt=opt, n_steps=ipf) for _ in range(reps)]
-        k_ms = sum(p[0] for p in pairs) / reps               # the dispatch's own begin -> end timestamps (hipExtLaunchKernel events):
-                                                             # the quantity a rocprofv3 --kernel-trace reports per dispatch (profiles/)
-        k_ms_pair = sum(p[1] for p in pairs) / reps          # a pair of stream events around the launch (includes the events' own cost)
         # which kernel ran and how the batch was cut: asked from the library (vmapstep_describe_plan), not re-derived here
         plan = op.plan()
         pk = plan["kernel"]
@@ -874,6 +921,39 @@ def main():
                         if on_bf16_pipe and args.weights == "f32" else
                         "; bf16 matrix pipe: one weight plane x three activation planes forward, 2 + 3 products backward" if on_bf16_pipe
                         else "; exact-fp32 matrix instruction"))
+        out = {
+            "full": args.full,
+            "metric": "training rays/sec (all objects) per step", "value": value, "unit": "rays/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "repeats": repeats_info,
+            "dtype": dtype_label, "data": "synthetic",
+            "config": {"workload": f"{args.config}: {n} objects/GPU x 4-layer/{H}-hidden MLP, {R} rays/object, "
+                                   f"{S} samples/ray, fwd+loss+bwd+fused AdamW, {ipf} steps per frame call",
+                       "objects_per_gpu": n, "rays_per_object": R, "samples_per_ray": S, "hidden": H,
+                       "parallelism": f"objects sharded over {world} GPU(s); no per-step collective, one 4x{ipf}-int32 flag all-reduce per frame"},
+            "preheat": {"ms": args.preheat_ms, "steps": preheat_steps, "timed": False},
+            "world": {"world_size": world, "devices": devices, "rccl": rccl_version, "backend": backend if dist else None,
+                      "ms_per_step_per_rank": per_rank_ms, "region_costs": region,
+                      "weak_scaling_prediction": ("objects shard with no collective on the step path; per frame ONE all_reduce(MAX) of 4 x steps int32 (a ring of "
+                                                  "latency-bound hops: 20-40 us at 8 ranks = 3-6 % of a 0.6 ms frame of 20 steps) => >= 7.5x at 8 GPUs expected against the "
+                                                  "north star's >= 6x (DESIGN.md section 4); measured cost of that collective and of a barrier: region_costs") if world > 1 else None},
+            "frame_call": ("marshalled per call" if bound is None else
+                           "bound (arguments marshalled once), replayed as a hipGraph per frame (device-resident optimiser step count)" if bound.graph
+                           else "bound (arguments marshalled once), launched kernel by kernel"),
+        }
+    if rank == 0 and args.full:
+        # ---- dominant kernel, timed live on the launch stream ----
+        # (event pairs around every launch of the dominant kernel inside the real prep / main / finalize sequence; `frac`
+        # uses the RAW pair time, which is what a rocprofv3 --kernel-trace of the same command reports per dispatch
+        # (profiles/); the time minus the cost of an empty event pair and back-to-back launches of the kernel alone are
+        # reported next to it)
+        b0 = tuple(x[:, :R] for x in fargs)
+        k_ms_alone = op.profile_main_kernel(tfc, tB, tsc, *b0, reps=args.profile_reps)
+        reps = max(1, args.profile_reps // ipf)
+        pairs = [op.profile_train_steps(tfc, tB, tsc, *fargs, opt=opt, n_steps=ipf) for _ in range(reps)]
+        k_ms = sum(p[0] for p in pairs) / reps               # the dispatch's own begin -> end timestamps (hipExtLaunchKernel events):
+                                                             # the quantity a rocprofv3 --kernel-trace reports per dispatch (profiles/)
+        k_ms_pair = sum(p[1] for p in pairs) / reps          # a pair of stream events around the launch (includes the events' own cost)
         flops = layout.step_flops(n, R, S, H)
         abytes = layout.step_bytes(n, R, S, H)
         achieved = flops / (k_ms * 1e-3) / 1e12
@@ -1016,15 +1096,7 @@ def main():
                               ": separate FETCH_SIZE / WRITE_SIZE passes over tests/tools/run_steps.py, FETCH doubled per MI355X_MICROARCH.md), not observed in this run")
         else:
             traffic_source = traffic_note
-        out = {
-            "metric": "training rays/sec (all objects) per step", "value": value, "unit": "rays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "repeats": repeats_info,
-            "dtype": dtype_label, "data": "synthetic",
-            "config": {"workload": f"{args.config}: {n} objects/GPU x 4-layer/{H}-hidden MLP, {R} rays/object, "
-                                   f"{S} samples/ray, fwd+loss+bwd+fused AdamW, {ipf} steps per frame call",
-                       "objects_per_gpu": n, "rays_per_object": R, "samples_per_ray": S, "hidden": H,
-                       "parallelism": f"objects sharded over {world} GPU(s); no per-step collective, one 4x{ipf}-int32 flag all-reduce per frame"},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": kernel_name, "achieved": achieved,
                          "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFLOPS,
                          "frac_is": "fp32-EQUIVALENT: algorithmic float32 FLOPs (n R S 6 H (4H + 220)) per launch / launch duration / the float32 "
@@ -1048,21 +1120,12 @@ def main():
             "value_exact_fp32_kernel": exact,
             "value_fp32_equivalent_backward": bwd6,
             "fwd_bwd_only": {"ms_per_step_host_launched": fb_ms, "rays_per_s": n * R / (fb_ms * 1e-3)},
-            "preheat": {"ms": args.preheat_ms, "steps": preheat_steps, "timed": False},
             "with_background": with_bg,
-            "world": {"world_size": world, "devices": devices, "rccl": rccl_version, "backend": backend if dist else None,
-                      "ms_per_step_per_rank": per_rank_ms, "region_costs": region,
-                      "weak_scaling_prediction": ("objects shard with no collective on the step path; per frame ONE all_reduce(MAX) of 4 x steps int32 (a ring of "
-                                                  "latency-bound hops: 20-40 us at 8 ranks = 3-6 % of a 0.6 ms frame of 20 steps) => >= 7.5x at 8 GPUs expected against the "
-                                                  "north star's >= 6x (DESIGN.md section 4); measured cost of that collective and of a barrier: region_costs") if world > 1 else None},
             "frame": None,
-            "frame_call": ("marshalled per call" if bound is None else
-                           "bound (arguments marshalled once), replayed as a hipGraph per frame (device-resident optimiser step count)" if bound.graph
-                           else "bound (arguments marshalled once), launched kernel by kernel"),
-        }
+        })
     if dist:
         td.barrier()
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_gpu_baseline:
             # the north star's ">= 5x the reference single-GPU PyTorch path": the reference's OWN vmap step on this GPU, timed live
             try:
@@ -1120,7 +1183,7 @@ def main():
     # ---- the shared background model next to the objects (N > 1, or --with-background): AFTER everything the scored line needs,
     #      under a watchdog - this path (RCCL on a side stream, one communicator shared with the objects' flag reduction) has
     #      never run on an 8-GPU node, and a hang or an exception in it must not take `value` with it ----
-    if (args.with_background or world > 1) and not args.no_background:
+    if (args.with_background or (world > 1 and args.full)) and not args.no_background:
         def on_timeout():
             if rank == 0:
                 out["with_background"] = {"error": f"watchdog: the background legs did not finish within {args.bg_timeout:.0f} s (objects-only `value` above is unaffected)"}
@@ -1142,7 +1205,7 @@ def main():
         td.barrier()
         td.destroy_process_group()       # (RCCL prints its version banner on stdout: the JSON line comes after it, last)
         dog.cancel()
-    if rank == 0 and world == 1 and not args.pmc_file and not args.no_pmc:
+    if rank == 0 and world == 1 and args.full and not args.pmc_file and not args.no_pmc:
         # HBM-side bytes per launch, OBSERVED for the library this process runs: two rocprofv3 --pmc subprocess passes.  LAST, and under
         # a watchdog: a slow or hung profiler can cost the observation (the line then keeps the committed counter file's figure and
         # says so), never the line

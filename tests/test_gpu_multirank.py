@@ -248,7 +248,7 @@ def test_bench_runs_with_two_ranks_on_one_gpu(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "40", "--warmup", "5",
            "--preheat-ms", "30", "--profile-reps", "20", "--no-cpu-baseline", "--no-gpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -274,7 +274,7 @@ def test_plain_bench_gpus_2_starts_its_own_ranks(tmp_path):
     env = dict(os.environ, VMAP_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR", "GROUP_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--preheat-ms", "30",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--preheat-ms", "30",
            "--profile-reps", "20", "--no-background"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -20,5 +20,5 @@ done
 cd $R
 PMC_WORKLOAD="tests/tools/run_steps.py $CFG 40 $WTS" python tests/tools/pmc_summary.py > $O/pmc_counters.json
 rm -rf gpurun_out/pmc
-python bench.py --config $CFG --weights $WTS --steps $STEPS --warmup $WARM --pmc-file $O/pmc_counters.json > $O/bench.json 2> $O/bench.err
+python bench.py --full --config $CFG --weights $WTS --steps $STEPS --warmup $WARM --pmc-file $O/pmc_counters.json > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json

@@ -11,7 +11,7 @@ timeout 300 python tests/tools/abl_probe.py background f32 2>&1 | grep "^{" | te
 timeout 300 python tests/tools/abl_probe.py imap_plumbing f32 2>&1 | grep "^{" | tee -a $O/probe.jsonl
 timeout 300 python tests/tools/abl_probe.py stress_rank8 bf16 2>&1 | grep "^{" | tee -a $O/probe.jsonl
 timeout 300 python tests/tools/abl_probe.py stress_256x64 bf16 2>&1 | grep "^{" | tee -a $O/probe.jsonl
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gpu-baseline --no-pmc > $O/bench_20_5.json 2> $O/bench_20_5.err; echo rc=$?
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gpu-baseline --no-pmc > $O/bench_20_5.json 2> $O/bench_20_5.err; echo rc=$?
 python - <<PY
 import json
 j = json.loads([l for l in open("gpurun_out/$T/bench_20_5.json").read().splitlines() if l.startswith("{")][-1])

@@ -2,7 +2,7 @@ set -x
 mkdir -p gpurun_out/r6i
 O=$PWD/gpurun_out/r6i
 # the N > 1 code path of bench.py on the REAL RCCL backend with one rank (the only way on a 1-GPU box), background legs included
-VMAP_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --with-background > $O/bench_rccl_world1.json 2> $O/bench_rccl_world1.err; echo rc=$?
+VMAP_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --with-background > $O/bench_rccl_world1.json 2> $O/bench_rccl_world1.err; echo rc=$?
 python - <<PY
 import json
 j = json.loads([l for l in open("gpurun_out/r6i/bench_rccl_world1.json").read().splitlines() if l.startswith("{")][-1])

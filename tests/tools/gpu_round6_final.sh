@@ -7,9 +7,9 @@ O=$PWD/gpurun_out/r6final
 R=$PWD
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest_gpu_tail.txt; cat $O/pytest_gpu_tail.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-VMAP_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_plain_gloo2.json 2> $O/bench_plain_gloo2.err; echo plain_gloo2 rc=$?
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+VMAP_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_plain_gloo2.json 2> $O/bench_plain_gloo2.err; echo plain_gloo2 rc=$?
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof205 -o hl -- python $R/bench.py --steps 20 --warmup 5 --timed-only > $O/prof_run205.log 2>&1 < /dev/null
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profbg -o hl -- python $R/bench.py --config background --steps 200 --warmup 20 --timed-only > $O/prof_runbg.log 2>&1 < /dev/null
