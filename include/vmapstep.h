@@ -309,6 +309,29 @@ int vmapstep_query_points(int32_t hidden, const vmapstep_params* params, const v
                           const float* points, int64_t n_points, const int64_t points_stride[2],
                           float* occupancy, float* color, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh extraction (the reference's Trainer.meshing, trainer.py:35-75) ---------------------------------------
+ * Marching cubes over a C-contiguous [nx][ny][nz] float32 volume at `level` (a corner is above iff value > level), on the device:
+ *   vmapstep_mesh_count  enqueues the count and the scan; writes the totals (vertices, faces) to the DEVICE int64[2] `counts`;
+ *   the caller reads them (the one host synchronisation per mesh), allocates the outputs and calls
+ *   vmapstep_mesh_emit   with the same volume, level and workspace: vertices [n_vertices][3] float32, normals [n_vertices][3]
+ *                        float32 (optional), faces [n_faces][3] int32.  Nothing is written at or past the capacities given.
+ * Output order (deterministic, bit-identical from call to call): vertices by the owning grid point (i*ny + j)*nz + k, then axis
+ * 0, 1, 2 of its crossing +axis edge; faces by cell, then the classic (Lorensen) table's order, winding as scikit-image's
+ * marching_cubes(method='lorensen', gradient_direction='ascent'); degenerate triangles are kept.
+ * `affine` (host, 12 floats, rows [A | b], may be NULL = index space) maps each index-space vertex v to A v + b; normals are
+ * numpy.gradient's stencil interpolated along the edge, negated (pointing to decreasing values), mapped by A^-T and normalised.
+ * Limits: 2 <= nx, ny, nz <= 1024 and 3*nx*ny*nz < 2^31 (VMAPSTEP_ERR_UNSUPPORTED otherwise); workspace 256-byte aligned and
+ * >= vmapstep_mesh_workspace_bytes(nx, ny, nz).
+ * vmapstep_mesh_grid_points writes the nx*ny*nz points A (i, j, k) + b as [n][3] float32 in C order (the grid Trainer.meshing
+ * queries: make_3D_grid, render_rays.py:98-122, with the scale, rotation, centre and -obj_center folded into one affine). */
+int vmapstep_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes);
+int vmapstep_mesh_grid_points(int32_t nx, int32_t ny, int32_t nz, const float affine[12], float* points, void* stream);
+int vmapstep_mesh_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float affine[12],
+                       float* vertices, float* normals, int32_t* faces, int64_t n_vertices, int64_t n_faces,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,5 +54,26 @@ int finalize_ws8(const vk::FinalizeArgs& f, const vk::FinalizeHot& h, const int*
 // k_misc.hip: inference query and the frame sampler
 int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, long long n_points, hipStream_t st);
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st);   // a.obj_max != null: the split form (two launches)
+
+// k_mesh.hip: marching cubes (mesh_kernels.h) and the dense grid Trainer.meshing queries.  The workspace of a [nx][ny][nz] volume:
+// per-workgroup (vertices, faces) int64 pairs, then the first vertex id (int32) and the crossing-edge mask (uint8) of every point.
+struct MeshLayout {
+    long long n; int nblk; size_t off_firstv, off_emask, bytes;
+};
+inline MeshLayout mesh_layout(int nx, int ny, int nz) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    MeshLayout l;
+    l.n = (long long)nx * ny * nz;
+    l.nblk = (int)((l.n + 255) / 256);          // = vm::kMeshWG points per workgroup (static_assert in k_mesh.hip)
+    l.off_firstv = up((size_t)l.nblk * 2 * sizeof(long long));
+    l.off_emask = l.off_firstv + up((size_t)l.n * sizeof(int));
+    l.bytes = l.off_emask + up((size_t)l.n);
+    return l;
+}
+int mesh_grid_points(int nx, int ny, int nz, const float affine[12], float* points, hipStream_t st);
+int mesh_count(const float* volume, int nx, int ny, int nz, float level, long long* counts, void* workspace, hipStream_t st);
+// affine / ninv: null = index space; otherwise [A | b] rows and the inverse transpose of A (rows, for the normals)
+int mesh_emit(const float* volume, int nx, int ny, int nz, float level, const float* affine, const float* ninv, float* vertices,
+              float* normals, int* faces, long long n_vertices, long long n_faces, void* workspace, hipStream_t st);
 
 }  // namespace vl

@@ -819,6 +819,69 @@ int vmapstep_query_points(int32_t hidden, const vmapstep_params* params, const v
     return vl::query_points(hidden, a, q, n_points, static_cast<hipStream_t>(stream));
 }
 
+static int check_mesh_shape(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || nx > 1024 || ny > 1024 || nz > 1024 || 3 * (long long)nx * ny * nz >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "mesh volume %dx%dx%d: each side 2..1024 and 3*nx*ny*nz < 2^31", nx, ny, nz);
+    return VMAPSTEP_OK;
+}
+
+static int check_mesh_workspace(int32_t nx, int32_t ny, int32_t nz, void* workspace, size_t workspace_bytes) {
+    const size_t need = vl::mesh_layout(nx, ny, nz).bytes;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "mesh workspace must be 256-byte aligned and >= %zu bytes", need);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    *bytes = vl::mesh_layout(nx, ny, nz).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_mesh_grid_points(int32_t nx, int32_t ny, int32_t nz, const float affine[12], float* points, void* stream) {
+    if (!affine || !points) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::mesh_grid_points(nx, ny, nz, affine, points, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_mesh_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!volume || !counts) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    if (int rc = check_mesh_workspace(nx, ny, nz, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::mesh_count(volume, nx, ny, nz, level, reinterpret_cast<long long*>(counts), workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float affine[12],
+                       float* vertices, float* normals, int32_t* faces, int64_t n_vertices, int64_t n_faces,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!volume || n_vertices < 0 || n_faces < 0 || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "null argument / negative count");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    if (int rc = check_mesh_workspace(nx, ny, nz, workspace, workspace_bytes)) return rc;
+    float ninv[9];
+    if (affine) {
+        // the normals' map: the inverse transpose of the linear part, in double
+        double m[9], inv[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) m[3 * r + c] = affine[4 * r + c];
+        inv[0] = m[4] * m[8] - m[5] * m[7]; inv[1] = m[2] * m[7] - m[1] * m[8]; inv[2] = m[1] * m[5] - m[2] * m[4];
+        inv[3] = m[5] * m[6] - m[3] * m[8]; inv[4] = m[0] * m[8] - m[2] * m[6]; inv[5] = m[2] * m[3] - m[0] * m[5];
+        inv[6] = m[3] * m[7] - m[4] * m[6]; inv[7] = m[1] * m[6] - m[0] * m[7]; inv[8] = m[0] * m[4] - m[1] * m[3];
+        const double det = m[0] * inv[0] + m[1] * inv[3] + m[2] * inv[6];
+        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return fail(VMAPSTEP_ERR_ARGUMENT, "mesh affine: singular linear part");
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) ninv[3 * r + c] = (float)(inv[3 * c + r] / det);     // (A^-1)^T
+    }
+    if (n_vertices == 0 && n_faces == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::mesh_emit(volume, nx, ny, nz, level, affine, affine ? ninv : nullptr, vertices, normals, faces, n_vertices, n_faces,
+                         workspace, static_cast<hipStream_t>(stream));
+}
+
 static_assert(sizeof(vmapstep_sample_object) == sizeof(vs::SampleObject), "sample object table layout");
 
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {

@@ -3,7 +3,8 @@
 ``Trainer(cfg)`` exposes ``fc_occ_map``, ``pe``, ``obj_scale``, ``device``, ``hidden_feature_size``, ``obj_id``
 and ``bound_extent`` so that code written against the reference's ``sceneObject.trainer`` keeps working.
 ``cfg`` is any object with the attributes the reference's ``cfg.Config`` provides (cfg.py:6-91).
-Mesh extraction (trainer.py:35-75) is outside the hot path and not provided; ``eval_points`` is.
+``meshing`` (trainer.py:35-75) and ``eval_points`` run on the device: the dense grid, the occupancy query, marching cubes
+(vmap_amd/meshing.py; its docstring lists the deviations from the reference's skimage / trimesh path) and the colour query.
 """
 from __future__ import annotations
 
@@ -28,6 +29,32 @@ class Trainer:
         self.fc_occ_map = fields.OccupancyMap(self.emb_size1, self.emb_size2, hidden_size=self.hidden_feature_size)
         self.fc_occ_map.apply(fields.init_weights).to(self.device)
         self.pe = fields.UniDirsEmbed(max_deg=self.n_unidir_funcs, scale=self.obj_scale).to(self.device)
+
+    @torch.no_grad()
+    def meshing(self, bound, obj_center, grid_dim=256):
+        """The reference's Trainer.meshing (trainer.py:35-75) on the device: grid_dim^3 grid points of the object box (scale
+        bound.extent / (2 bound_extent), rotation bound.R, centre bound.center, minus obj_center) -> eval_points -> marching cubes at
+        0.5 with the vertices mapped to scene coordinates (obj_center NOT subtracted, as in the reference) -> eval_points at the
+        vertices -> colours (color * 255) truncated to uint8.  ``bound``: anything with .extent, .center, .R (meshing.BoundingBox,
+        an open3d OrientedBoundingBox).  Returns a meshing.Mesh, or None where the reference returns None."""
+        from . import meshing
+        D = int(grid_dim)
+        dev = torch.device(self.device)
+        pts = meshing.grid_points((D, D, D), meshing.bound_affine(bound, self.bound_extent, D, obj_center), dev)
+        ret = self.eval_points(pts)
+        if ret is None:
+            return None
+        occ, _ = ret
+        del pts
+        mesh = meshing.extract_mesh(occ.view(D, D, D), 0.5, meshing.bound_affine(bound, self.bound_extent, D))
+        if mesh is None:
+            return None
+        ret = self.eval_points(mesh.vertices)
+        if ret is None:
+            return None
+        _, color = ret
+        mesh.vertex_colors = (color * 255).to(torch.uint8)
+        return mesh
 
     @torch.no_grad()
     def eval_points(self, points: torch.Tensor, chunk_size: int = 100000):
