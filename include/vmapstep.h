@@ -332,6 +332,53 @@ int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, 
                        float* vertices, float* normals, int32_t* faces, int64_t n_vertices, int64_t n_faces,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh evaluation (the reference's metric/eval_3D_obj.py:8-41 and metric/metrics.py: crop, sample, nearest neighbours) -------------
+ * Point sets are CSR-segmented: every call takes the offsets [n_sets + 1] (int64) twice, as a DEVICE array the kernels read and
+ * as a HOST array the library validates and plans the launch from (the two must hold the same values).  Offsets must be
+ * non-decreasing, start at >= 0 and end at <= the array's length; every array holds < 2^31 points (VMAPSTEP_ERR_ARGUMENT otherwise).
+ *
+ * vmapstep_nn_distance: for every query i of set s (queries [qo[s], qo[s+1])), dist[i] = the Euclidean distance to the nearest
+ * ref of the same set (refs [ro[s], ro[s+1])) and, when `index` is not NULL, index[i] = that ref's index into `refs` (ties: the
+ * smallest index).  Exhaustive; squared distances from coordinate differences (dx*dx + dy*dy + dz*dz in float32), dist = sqrtf of
+ * the minimum.  Bit-identical from call to call and independent of the launch geometry.  A set with no queries writes nothing;
+ * a set with queries and no refs is VMAPSTEP_ERR_ARGUMENT.  Workspace: 256-byte aligned, >= vmapstep_nn_workspace_bytes.
+ *
+ * vmapstep_surface_sample: trimesh.sample.sample_surface per set: the points [oo[s], oo[s+1]) lie on the faces [fo[s], fo[s+1])
+ * (vertex indices into `vertices`; an index outside [0, n_vertices) reads as the origin).  Face areas in float64, an inclusive
+ * per-set cumulative sum, face = searchsorted_left(cdf, u0 * total); (r1, r2) -> (1 - r1, 1 - r2) when r1 + r2 > 1; the point is
+ * v0 + r1 (v1 - v0) + r2 (v2 - v0) in float32.  Randoms: Philox4x32-10 keyed on `seed`, counter (point index within its set,
+ * set_base + s, stream_id, 0): u0 from 53 bits, r1 and r2 from 24 bits each - or, when `randoms` is not NULL, its u0 [N] float64
+ * and r [N][2] float32 (both required).  `face_index` [N] (optional) receives the chosen face.  A set with points and no faces
+ * is VMAPSTEP_ERR_ARGUMENT.  Workspace: 256-byte aligned, >= vmapstep_surface_sample_workspace_bytes(n_faces).
+ *
+ * vmapstep_clip_box_count / _emit: the faces cropped to the box `box` = centre[3], R[9] (row-major, columns = the box's axes),
+ * full extent[3]: each triangle is clipped against the box's 6 half-spaces by Sutherland-Hodgman (a vertex with signed distance
+ * >= 0 is kept, new vertices p + (s_p / (s_p - s_q)) (q - p) in scene coordinates) and the polygon fan-triangulated from its first
+ * vertex.  _count enqueues the count and writes the number of triangles to the DEVICE int64[1] `count`; the caller reads it,
+ * allocates and calls _emit with the same mesh, box and workspace: `triangles` [n_triangles][3][3] float32 in face order, then
+ * fan order (nothing written at or past n_triangles); a triangle inside the box is emitted bit-unchanged.
+ * Workspace: 256-byte aligned, >= vmapstep_clip_box_workspace_bytes(n_faces). */
+typedef struct vmapstep_surface_randoms {
+    const double* u0; /* [N] uniforms in [0, 1): the face */
+    const float* r;   /* [N][2] uniforms in [0, 1): the barycentric pair */
+} vmapstep_surface_randoms;
+
+int vmapstep_nn_workspace_bytes(int64_t n_queries, int32_t n_sets, size_t* bytes);
+int vmapstep_nn_distance(const float* queries, int64_t n_queries, const int64_t* query_offsets, const int64_t* query_offsets_host,
+                         const float* refs, int64_t n_refs, const int64_t* ref_offsets, const int64_t* ref_offsets_host, int32_t n_sets,
+                         float* dist, int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_surface_sample_workspace_bytes(int64_t n_faces, size_t* bytes);
+int vmapstep_surface_sample(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                            const int64_t* face_offsets, const int64_t* face_offsets_host, const int64_t* out_offsets,
+                            const int64_t* out_offsets_host, int32_t n_sets, uint64_t seed, uint32_t stream_id, int32_t set_base,
+                            const vmapstep_surface_randoms* randoms, float* points, int32_t* face_index,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_clip_box_workspace_bytes(int64_t n_faces, size_t* bytes);
+int vmapstep_clip_box_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15],
+                            int64_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_clip_box_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15],
+                           float* triangles, int64_t n_triangles, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -92,6 +92,10 @@ class SampleRandoms(ctypes.Structure):
                 ("g_z", ctypes.c_void_p)]
 
 
+class SurfaceRandoms(ctypes.Structure):
+    _fields_ = [("u0", ctypes.c_void_p), ("r", ctypes.c_void_p)]
+
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -100,6 +104,8 @@ EXPORTS = (
     "vmapstep_query_workspace_bytes", "vmapstep_query_points", "vmapstep_profile_train_steps", "vmapstep_adamw_apply",
     "vmapstep_sample_workspace_bytes", "vmapstep_describe_plan", "vmapstep_sample_frame_rays",
     "vmapstep_mesh_workspace_bytes", "vmapstep_mesh_grid_points", "vmapstep_mesh_count", "vmapstep_mesh_emit",
+    "vmapstep_nn_workspace_bytes", "vmapstep_nn_distance", "vmapstep_surface_sample_workspace_bytes", "vmapstep_surface_sample",
+    "vmapstep_clip_box_workspace_bytes", "vmapstep_clip_box_count", "vmapstep_clip_box_emit",
 )
 
 _libs = {}
@@ -181,13 +187,29 @@ def load(path=None):
     lib.vmapstep_mesh_emit.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_nn_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_nn_distance.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_surface_sample_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_surface_sample.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(SurfaceRandoms),
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_clip_box_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_clip_box_count.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_float),
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_clip_box_emit.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_float),
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("vmapstep_describe_plan", "vmapstep_param_layout", "vmapstep_workspace_bytes", "vmapstep_fwd_bwd", "vmapstep_render",
                "vmapstep_train_steps", "vmapstep_profile_main_kernel",
                "vmapstep_profile_phases", "vmapstep_prepare", "vmapstep_train_steps_prepared",
                "vmapstep_workspace_counts_offset", "vmapstep_fwd_bwd_prepared", "vmapstep_sample_frame",
                "vmapstep_query_workspace_bytes", "vmapstep_query_points", "vmapstep_profile_train_steps", "vmapstep_adamw_apply",
                "vmapstep_sample_workspace_bytes", "vmapstep_sample_frame_rays", "vmapstep_mesh_workspace_bytes", "vmapstep_mesh_grid_points",
-               "vmapstep_mesh_count", "vmapstep_mesh_emit"):
+               "vmapstep_mesh_count", "vmapstep_mesh_emit", "vmapstep_nn_workspace_bytes", "vmapstep_nn_distance",
+               "vmapstep_surface_sample_workspace_bytes", "vmapstep_surface_sample", "vmapstep_clip_box_workspace_bytes",
+               "vmapstep_clip_box_count", "vmapstep_clip_box_emit"):
         getattr(lib, fn).restype = ctypes.c_int
     if lib.vmapstep_abi_version() != ABI_VERSION:
         raise VmapStepError(f"ABI mismatch: library {lib.vmapstep_abi_version()} != binding {ABI_VERSION}")

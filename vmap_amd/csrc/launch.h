@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,5 +75,57 @@ int mesh_count(const float* volume, int nx, int ny, int nz, float level, long lo
 // affine / ninv: null = index space; otherwise [A | b] rows and the inverse transpose of A (rows, for the normals)
 int mesh_emit(const float* volume, int nx, int ny, int nz, float level, const float* affine, const float* ninv, float* vertices,
               float* normals, int* faces, long long n_vertices, long long n_faces, void* workspace, hipStream_t st);
+
+// k_eval.hip: mesh evaluation (eval_kernels.h).  Nearest neighbours: the workspace holds the per-set prefix of the work items
+// (int64 [n_sets + 1]) and one packed (squared distance, index) key per query (uint64 [n_queries]).
+struct NnLayout {
+    size_t off_keys, bytes;
+};
+inline NnLayout nn_layout(long long n_queries, int n_sets) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    NnLayout l;
+    l.off_keys = up((size_t)(n_sets + 1) * sizeof(long long));
+    l.bytes = l.off_keys + up((size_t)n_queries * sizeof(unsigned long long));
+    return l;
+}
+// The launch plan from the host copies of the offsets: refs per work item (a multiple of the 512-ref tile, ve::kNnTile) chosen so
+// that about kNnItemsTarget items exist (8 per CU), and the item count nn_plan computes on the device by the same formula.
+struct NnPlan {
+    long long n_queries, q_begin, q_end, rchunk, items;
+};
+constexpr long long kNnItemsTarget = 2048;
+inline NnPlan nn_plan_host(const long long* qo, const long long* ro, int n_sets, long long n_queries) {
+    constexpr long long qb = 2048, tile = 512;            // = ve::kNnQB, ve::kNnTile (static_assert in k_eval.hip)
+    NnPlan p;
+    p.n_queries = n_queries; p.q_begin = qo[0]; p.q_end = qo[n_sets];
+    long long work = 0;                                   // sum over sets of (query blocks x refs)
+    for (int s = 0; s < n_sets; ++s) {
+        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
+        if (nq > 0) work += (nq + qb - 1) / qb * nr;
+    }
+    long long rc = (work + kNnItemsTarget - 1) / kNnItemsTarget;
+    rc = rc < 2 * tile ? 2 * tile : rc;
+    rc = (rc + tile - 1) / tile * tile;
+    p.rchunk = rc;
+    p.items = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
+        if (nq > 0 && nr > 0) p.items += ((nq + qb - 1) / qb) * ((nr + rc - 1) / rc);
+    }
+    return p;
+}
+int nn_distance(const NnPlan& p, const float* queries, const long long* qo, const float* refs, const long long* ro, int n_sets,
+                float* dist, int* index, void* workspace, hipStream_t st);
+// surface sampling: the workspace is the float64 cumulative area of every face
+inline size_t surface_sample_bytes(long long n_faces) { return ((size_t)n_faces * sizeof(double) + 255) / 256 * 256; }
+int surface_sample(const float* vertices, long long n_vertices, const int* faces, const long long* fo, const long long* oo, int n_sets,
+                   long long o_begin, long long o_end, unsigned long long seed, unsigned stream_id, int set_base, const double* u0,
+                   const float* r, float* points, int* face_index, void* workspace, hipStream_t st);
+// box clipping: the workspace is one int64 per 256 faces (triangles per block, then their exclusive prefix)
+inline size_t clip_box_bytes(long long n_faces) { return (((size_t)(n_faces + 255) / 256) * sizeof(long long) + 255) / 256 * 256 + 256; }
+int clip_box_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float box[15], long long* count,
+                   void* workspace, hipStream_t st);
+int clip_box_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float box[15], float* triangles,
+                  long long n_triangles, void* workspace, hipStream_t st);
 
 }  // namespace vl

@@ -882,6 +882,114 @@ int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, 
                          workspace, static_cast<hipStream_t>(stream));
 }
 
+static int check_eval_workspace(void* workspace, size_t workspace_bytes, size_t need, const char* what) {
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "%s workspace must be 256-byte aligned and >= %zu bytes", what, need);
+    return VMAPSTEP_OK;
+}
+
+// the host copy of a CSR offset array over an array of n elements: non-decreasing, inside [0, n], n < 2^31
+static int check_offsets(const int64_t* off, int32_t n_sets, int64_t n, const char* what) {
+    if (!off) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: host offsets are null", what);
+    if (n < 0 || n >= (1ll << 31)) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: %lld points (0 .. 2^31 - 1 per array)", what, (long long)n);
+    if (off[0] < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: offsets start below 0", what);
+    for (int32_t s = 0; s < n_sets; ++s)
+        if (off[s + 1] < off[s]) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: offsets decrease at set %d", what, (int)s);
+    if (off[n_sets] > n) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: offsets run past the array (%lld > %lld)", what, (long long)off[n_sets], (long long)n);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_nn_workspace_bytes(int64_t n_queries, int32_t n_sets, size_t* bytes) {
+    if (!bytes || n_queries < 0 || n_queries >= (1ll << 31) || n_sets < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / negative argument");
+    *bytes = vl::nn_layout(n_queries, n_sets).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_nn_distance(const float* queries, int64_t n_queries, const int64_t* query_offsets, const int64_t* query_offsets_host,
+                         const float* refs, int64_t n_refs, const int64_t* ref_offsets, const int64_t* ref_offsets_host, int32_t n_sets,
+                         float* dist, int32_t* index, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_sets < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "n_sets must be >= 1");
+    if (int rc = check_offsets(query_offsets_host, n_sets, n_queries, "nn queries")) return rc;
+    if (int rc = check_offsets(ref_offsets_host, n_sets, n_refs, "nn refs")) return rc;
+    const int64_t* qo = query_offsets_host;
+    const int64_t* ro = ref_offsets_host;
+    for (int32_t s = 0; s < n_sets; ++s)
+        if (qo[s + 1] > qo[s] && ro[s + 1] == ro[s]) return fail(VMAPSTEP_ERR_ARGUMENT, "nn set %d has queries and no refs", (int)s);
+    if (qo[n_sets] == qo[0]) return VMAPSTEP_OK;           // no query anywhere: nothing to write
+    if (!queries || !refs || !query_offsets || !ref_offsets || !dist) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::nn_layout(n_queries, n_sets).bytes, "nn")) return rc;
+    const vl::NnPlan plan = vl::nn_plan_host(reinterpret_cast<const long long*>(qo), reinterpret_cast<const long long*>(ro), n_sets, n_queries);
+    if (plan.items >= (1ll << 31)) return fail(VMAPSTEP_ERR_UNSUPPORTED, "nn: %lld work items", (long long)plan.items);
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::nn_distance(plan, queries, reinterpret_cast<const long long*>(query_offsets), refs, reinterpret_cast<const long long*>(ref_offsets),
+                           n_sets, dist, index, workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_surface_sample_workspace_bytes(int64_t n_faces, size_t* bytes) {
+    if (!bytes || n_faces < 0 || n_faces >= (1ll << 31)) return fail(VMAPSTEP_ERR_ARGUMENT, "null / negative argument");
+    *bytes = vl::surface_sample_bytes(n_faces);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_surface_sample(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                            const int64_t* face_offsets, const int64_t* face_offsets_host, const int64_t* out_offsets,
+                            const int64_t* out_offsets_host, int32_t n_sets, uint64_t seed, uint32_t stream_id, int32_t set_base,
+                            const vmapstep_surface_randoms* randoms, float* points, int32_t* face_index,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_sets < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "n_sets must be >= 1");
+    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return fail(VMAPSTEP_ERR_ARGUMENT, "surface sample: %lld vertices", (long long)n_vertices);
+    if (int rc = check_offsets(face_offsets_host, n_sets, n_faces, "surface sample faces")) return rc;
+    if (int rc = check_offsets(out_offsets_host, n_sets, (1ll << 31) - 1, "surface sample points")) return rc;
+    const int64_t* fo = face_offsets_host;
+    const int64_t* oo = out_offsets_host;
+    for (int32_t s = 0; s < n_sets; ++s)
+        if (oo[s + 1] > oo[s] && fo[s + 1] == fo[s]) return fail(VMAPSTEP_ERR_ARGUMENT, "surface sample set %d has points and no faces", (int)s);
+    if (randoms && (!randoms->u0 || !randoms->r)) return fail(VMAPSTEP_ERR_ARGUMENT, "surface sample randoms: u0 and r are both required");
+    if (oo[n_sets] == oo[0]) return VMAPSTEP_OK;
+    if (!vertices || !faces || !face_offsets || !out_offsets || !points) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::surface_sample_bytes(n_faces), "surface sample")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::surface_sample(vertices, n_vertices, faces, reinterpret_cast<const long long*>(face_offsets),
+                              reinterpret_cast<const long long*>(out_offsets), n_sets, oo[0], oo[n_sets], seed, stream_id, set_base,
+                              randoms ? randoms->u0 : nullptr, randoms ? randoms->r : nullptr, points, face_index, workspace,
+                              static_cast<hipStream_t>(stream));
+}
+
+static int check_clip(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15]) {
+    if (n_vertices < 0 || n_vertices >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "clip box: counts 0 .. 2^31 - 1");
+    if (!box || (n_faces > 0 && (!vertices || !faces))) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    for (int i = 0; i < 15; ++i)
+        if (!std::isfinite(box[i])) return fail(VMAPSTEP_ERR_ARGUMENT, "clip box: non-finite box");
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_clip_box_workspace_bytes(int64_t n_faces, size_t* bytes) {
+    if (!bytes || n_faces < 0 || n_faces >= (1ll << 31)) return fail(VMAPSTEP_ERR_ARGUMENT, "null / negative argument");
+    *bytes = vl::clip_box_bytes(n_faces);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_clip_box_count(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15],
+                            int64_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_clip(vertices, n_vertices, faces, n_faces, box)) return rc;
+    if (!count) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::clip_box_bytes(n_faces), "clip box")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::clip_box_count(vertices, n_vertices, faces, n_faces, box, reinterpret_cast<long long*>(count), workspace,
+                              static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_clip_box_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15],
+                           float* triangles, int64_t n_triangles, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_clip(vertices, n_vertices, faces, n_faces, box)) return rc;
+    if (n_triangles < 0 || (n_triangles > 0 && !triangles)) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument / negative count");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::clip_box_bytes(n_faces), "clip box")) return rc;
+    if (n_triangles == 0 || n_faces == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::clip_box_emit(vertices, n_vertices, faces, n_faces, box, triangles, n_triangles, workspace, static_cast<hipStream_t>(stream));
+}
+
 static_assert(sizeof(vmapstep_sample_object) == sizeof(vs::SampleObject), "sample object table layout");
 
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {

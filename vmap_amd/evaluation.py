@@ -1,0 +1,285 @@
+"""Mesh evaluation on the device: the reference's metric/eval_3D_obj.py:8-41 (calc_3d_metric) and metric/metrics.py (accuracy,
+completion, completion_ratio, chamfer) without trimesh or scipy.
+
+The work is three kernel families of csrc/eval_kernels.h: cropping to an oriented box (vmapstep_clip_box_count / _emit, instead of
+trimesh's slice_plane), area-weighted surface sampling (vmapstep_surface_sample, trimesh.sample.sample_surface's algorithm) and
+exhaustive nearest neighbours (vmapstep_nn_distance, instead of scipy's cKDTree.query); means and ratios are reduced in float64.
+Deviations from the reference, all deliberate:
+- the random stream: Philox4x32-10 keyed on ``seed`` (u0 from 53 bits, r1 and r2 from 24 bits), not numpy's global generator, so
+  samples are reproducible per (seed, stream, set) but differ from trimesh's draw for draw;
+- the default box (``box=None``): the principal-axes box of the GT vertices (covariance eigenvectors, extents from the
+  projections), not trimesh's minimum-volume ``oriented_bounds``; a caller after parity passes trimesh's box as a
+  ``meshing.BoundingBox`` (centre = inverse transform's translation, R = its rotation, extent = the extents);
+- cropping triangulates each clipped polygon as a fan from its first vertex, where trimesh's slice_plane triangulates otherwise:
+  the cropped surface and its area are the same, so the sampling distribution is the same;
+- sample coordinates are float32 (trimesh's are float64); the nearest-neighbour distances are float32 sqrtf of a float32 minimum.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+from .meshing import BoundingBox, Mesh, load_mesh
+
+__all__ = ["accuracy", "completion", "completion_ratio", "chamfer", "nn_distance", "sample_surface", "crop_to_box",
+           "principal_axes_box", "calc_3d_metric", "calc_3d_metrics"]
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise _lib.VmapStepError("mesh evaluation runs on the GPU (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _points(x, device):
+    """[n,3] contiguous float32 on the device from a numpy array or a tensor."""
+    t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
+    t = t.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    return t
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _aligned(nbytes, device):
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
+
+
+def _offsets(sizes, device):
+    host = np.zeros(len(sizes) + 1, np.int64)
+    host[1:] = np.cumsum(np.asarray(sizes, np.int64))
+    return host, torch.from_numpy(host).to(device)
+
+
+def _i64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def nn_distance(queries, refs, query_sizes=None, ref_sizes=None, return_index=False):
+    """Euclidean distance from every query to its nearest ref of the same set, as a float32 device tensor (and the int32 index
+    into ``refs`` of that ref, ties to the smallest index, with ``return_index``).  ``query_sizes`` / ``ref_sizes``: the sets'
+    sizes (CSR order); default one set.  One vmapstep_nn_distance call for all sets."""
+    lib = _lib.load()
+    dev = _device()
+    q, r = _points(queries, dev), _points(refs, dev)
+    qs = [len(q)] if query_sizes is None else [int(x) for x in query_sizes]
+    rs = [len(r)] if ref_sizes is None else [int(x) for x in ref_sizes]
+    if len(qs) != len(rs):
+        raise _lib.VmapStepError("nn_distance: query_sizes and ref_sizes need one entry per set")
+    qo_h, qo_d = _offsets(qs, dev)
+    ro_h, ro_d = _offsets(rs, dev)
+    dist = torch.empty(len(q), dtype=torch.float32, device=dev)
+    index = torch.empty(len(q), dtype=torch.int32, device=dev) if return_index else None
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.vmapstep_nn_workspace_bytes(len(q), len(qs), ctypes.byref(nb)), lib)
+    ws, ws_ptr = _aligned(nb.value, dev)
+    _lib.check(lib.vmapstep_nn_distance(q.data_ptr(), len(q), qo_d.data_ptr(), _i64p(qo_h), r.data_ptr(), len(r), ro_d.data_ptr(),
+                                        _i64p(ro_h), len(qs), dist.data_ptr(), None if index is None else index.data_ptr(), ws_ptr,
+                                        nb.value, _stream(dev)), lib)
+    del ws
+    return (dist, index) if return_index else dist
+
+
+def _mean(d):
+    return float(d.double().mean())
+
+
+def accuracy(gt_points, rec_points):
+    """Mean distance from the reconstruction's points to the GT points (metrics.py: accuracy)."""
+    return _mean(nn_distance(rec_points, gt_points))
+
+
+def completion(gt_points, rec_points):
+    """Mean distance from the GT points to the reconstruction's points (metrics.py: completion)."""
+    return _mean(nn_distance(gt_points, rec_points))
+
+
+def completion_ratio(gt_points, rec_points, dist_th=0.01):
+    """Fraction of GT points whose distance to the reconstruction is strictly below ``dist_th`` (metrics.py: completion_ratio)."""
+    return float((nn_distance(gt_points, rec_points) < dist_th).double().mean())
+
+
+def chamfer(gt_points, rec_points):
+    """(completion + accuracy) / 2 (metrics.py: chamfer), both directions in one launch."""
+    dev = _device()
+    g, r = _points(gt_points, dev), _points(rec_points, dev)
+    d = nn_distance(torch.cat([g, r]), torch.cat([r, g]), [len(g), len(r)], [len(r), len(g)])
+    return (_mean(d[:len(g)]) + _mean(d[len(g):])) / 2.0
+
+
+def _mesh_arrays(mesh, device):
+    v = _points(mesh.vertices, device)
+    f = torch.as_tensor(mesh.faces).to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    return v, f
+
+
+def _sample_sets(meshes, counts, seed=0, stream_id=0, set_base=0, randoms=None, return_face_index=False):
+    """One vmapstep_surface_sample call: counts[s] points on meshes[s], [sum(counts), 3] float32 (and the face index into each
+    mesh's own faces with ``return_face_index``).  ``randoms``: (u0 float64 [N], r float32 [N, 2]) device tensors (test mode)."""
+    lib = _lib.load()
+    dev = _device()
+    vs, fs, vbase = [], [], 0
+    for m in meshes:
+        v, f = _mesh_arrays(m, dev)
+        vs.append(v)
+        fs.append(f + vbase)
+        vbase += len(v)
+    v = torch.cat(vs) if len(vs) > 1 else vs[0]
+    f = torch.cat(fs) if len(fs) > 1 else fs[0]
+    fo_h, fo_d = _offsets([len(x) for x in fs], dev)
+    oo_h, oo_d = _offsets(counts, dev)
+    n = int(oo_h[-1])
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    fidx = torch.empty(n, dtype=torch.int32, device=dev) if return_face_index else None
+    rnd = None
+    if randoms is not None:
+        u0 = torch.as_tensor(randoms[0]).to(device=dev, dtype=torch.float64).contiguous()
+        rr = torch.as_tensor(randoms[1]).to(device=dev, dtype=torch.float32).contiguous()
+        if u0.numel() != n or rr.numel() != 2 * n:
+            raise _lib.VmapStepError("sample randoms: u0 [N] and r [N, 2]")
+        rnd = _lib.SurfaceRandoms(u0.data_ptr(), rr.data_ptr())
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.vmapstep_surface_sample_workspace_bytes(len(f), ctypes.byref(nb)), lib)
+    ws, ws_ptr = _aligned(nb.value, dev)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    _lib.check(lib.vmapstep_surface_sample(v.data_ptr(), len(v), f.data_ptr(), len(f), fo_d.data_ptr(), _i64p(fo_h), oo_d.data_ptr(),
+                                           _i64p(oo_h), len(fs), seed, int(stream_id), int(set_base),
+                                           None if rnd is None else ctypes.byref(rnd), pts.data_ptr(),
+                                           None if fidx is None else fidx.data_ptr(), ws_ptr, nb.value, _stream(dev)), lib)
+    del ws
+    if return_face_index:
+        return pts, fidx - torch.as_tensor(np.repeat(fo_h[:-1], counts), device=dev, dtype=torch.int32)
+    return pts
+
+
+def sample_surface(mesh, n, seed=0, stream_id=0, set_index=0):
+    """``n`` points drawn on ``mesh`` (a ``meshing.Mesh`` or anything with ``vertices`` / ``faces``) with probability proportional
+    to area, as a [n, 3] float32 device tensor: trimesh.sample.sample_surface's algorithm with a Philox stream keyed on ``seed``
+    and counted on (point, ``set_index``, ``stream_id``)."""
+    return _sample_sets([mesh], [int(n)], seed, stream_id, set_index)
+
+
+def _box15(box):
+    c = np.asarray(box.center, np.float64).reshape(3)
+    R = np.asarray(box.R, np.float64).reshape(3, 3)
+    e = np.asarray(box.extent, np.float64).reshape(3)
+    return (ctypes.c_float * 15)(*np.concatenate([c, R.reshape(-1), e]).astype(np.float32).tolist())
+
+
+def crop_to_box(mesh, box):
+    """The part of ``mesh`` inside ``box`` (``meshing.BoundingBox``: centre, R with the box's axes as columns, full extent) as a
+    ``Mesh`` of separate triangles (vertices [3T, 3], faces [[0,1,2], [3,4,5], ...], no normals), or ``None`` when nothing is left.
+    Each face is clipped against the box's six half-spaces; faces inside the box are kept bit-unchanged."""
+    lib = _lib.load()
+    dev = _device()
+    v, f = _mesh_arrays(mesh, dev)
+    b = _box15(box)
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.vmapstep_clip_box_workspace_bytes(len(f), ctypes.byref(nb)), lib)
+    ws, ws_ptr = _aligned(nb.value, dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    stream = _stream(dev)
+    _lib.check(lib.vmapstep_clip_box_count(v.data_ptr(), len(v), f.data_ptr(), len(f), b, count.data_ptr(), ws_ptr, nb.value, stream), lib)
+    t = int(count.cpu())                    # the one host synchronisation
+    if t == 0:
+        return None
+    tri = torch.empty(t, 3, 3, dtype=torch.float32, device=dev)
+    _lib.check(lib.vmapstep_clip_box_emit(v.data_ptr(), len(v), f.data_ptr(), len(f), b, tri.data_ptr(), t, ws_ptr, nb.value, stream), lib)
+    del ws
+    faces = torch.arange(3 * t, dtype=torch.int32, device=dev).reshape(t, 3)
+    return Mesh(tri.reshape(-1, 3), faces, None)
+
+
+def principal_axes_box(vertices):
+    """The box used when no GT box is given: axes = eigenvectors of the vertices' covariance (a right-handed R, columns),
+    extents = the range of the projections, centre = the middle of that range.  Not trimesh's minimum-volume oriented_bounds."""
+    p = torch.as_tensor(vertices).detach().to("cpu", torch.float64).reshape(-1, 3).numpy()
+    mu = p.mean(0)
+    _, vec = np.linalg.eigh(np.cov((p - mu).T))
+    R = vec[:, ::-1].copy()
+    if np.linalg.det(R) < 0:
+        R[:, 2] = -R[:, 2]
+    proj = (p - mu) @ R
+    lo, hi = proj.min(0), proj.max(0)
+    return BoundingBox(center=mu + R @ ((lo + hi) / 2), R=R, extent=hi - lo)
+
+
+def _enlarged(box):
+    return BoundingBox(center=box.center, R=box.R, extent=np.asarray(box.extent, np.float64) / 0.9)
+
+
+def calc_3d_metrics(pairs, N=200000, seed=0):
+    """``calc_3d_metric`` for a list of (mesh_rec, mesh_gt, box or None) tuples, pair k drawing its samples as ``index=k``.
+    Sampling is one call for all recs and one for all GTs; the nearest neighbours of both directions of every pair are ONE
+    vmapstep_nn_distance launch.  Returns one entry per pair: [[acc], [comp], [ratio_1cm], [ratio_5cm]], or None where the crop
+    leaves nothing - entry k equals ``calc_3d_metric(rec_k, gt_k, N, box_k, seed, index=k)``."""
+    return _metrics([(rec, gt, box, k) for k, (rec, gt, box) in enumerate(pairs)], int(N), seed)
+
+
+def calc_3d_metric(mesh_rec, mesh_gt, N=200000, box=None, seed=0, index=0):
+    """eval_3D_obj.py:8-41 on the device: crop ``mesh_rec`` to ``box`` (default: ``principal_axes_box`` of the GT vertices)
+    enlarged by 1/0.9, sample N points on each mesh, and return [[accuracy], [completion], [ratio < 1 cm], [ratio < 5 cm]], or None
+    when the crop leaves nothing.  The samples are Philox streams keyed on ``seed`` and counted on (point, ``index``, 0 for the
+    reconstruction / 1 for the GT)."""
+    return _metrics([(mesh_rec, mesh_gt, box, int(index))], int(N), seed)[0]
+
+
+def _metrics(items, N, seed):
+    crops, gts, keep, where = [], [], [], []
+    for i, (rec, gt, box, k) in enumerate(items):
+        b = principal_axes_box(gt.vertices) if box is None else box
+        c = crop_to_box(rec, _enlarged(b))
+        if c is not None:
+            crops.append(c)
+            gts.append(gt)
+            keep.append(k)
+            where.append(i)
+    out = [None] * len(items)
+    if not keep:
+        return out
+    if keep == list(range(keep[0], keep[0] + len(keep))):
+        # consecutive set indices: one segmented sampling call per stream (its sets are numbered keep[0] + s)
+        rec_pts = _sample_sets(crops, [N] * len(keep), seed, 0, keep[0])
+        gt_pts = _sample_sets(gts, [N] * len(keep), seed, 1, keep[0])
+    else:
+        rec_pts = torch.cat([_sample_sets([c], [N], seed, 0, k) for c, k in zip(crops, keep)])
+        gt_pts = torch.cat([_sample_sets([g], [N], seed, 1, k) for g, k in zip(gts, keep)])
+    n = len(keep)
+    # queries: rec_0 .. rec_{n-1}, gt_0 .. gt_{n-1}; refs: gt_0 .. gt_{n-1}, rec_0 .. rec_{n-1}
+    d = nn_distance(torch.cat([rec_pts, gt_pts]), torch.cat([gt_pts, rec_pts]), [N] * (2 * n), [N] * (2 * n))
+    d = d.reshape(2, n, N).double()
+    acc = d[0].mean(1).cpu().numpy()
+    comp = d[1].mean(1).cpu().numpy()
+    r1 = (d[1] < 0.01).double().mean(1).cpu().numpy()
+    r5 = (d[1] < 0.05).double().mean(1).cpu().numpy()
+    for j, i in enumerate(where):
+        out[i] = [[float(acc[j])], [float(comp[j])], [float(r1[j])], [float(r5[j])]]
+    return out
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m vmap_amd.evaluation", description="accuracy / completion / completion ratio of a mesh")
+    ap.add_argument("rec")
+    ap.add_argument("gt")
+    ap.add_argument("--n", type=int, default=200000)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    m = calc_3d_metric(load_mesh(args.rec), load_mesh(args.gt), N=args.n, seed=args.seed)
+    if m is None:
+        print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None}))
+        return 1
+    print(json.dumps({"rec": args.rec, "gt": args.gt, "n": args.n, "seed": args.seed, "accuracy": m[0][0], "completion": m[1][0],
+                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0]}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -34,7 +34,8 @@ class BoundingBox:
 
 
 class Mesh:
-    """Device tensors: vertices float32 [V,3], faces int32 [F,3], vertex_normals float32 [V,3], vertex_colors uint8 [V,3] or None."""
+    """Device tensors: vertices float32 [V,3], faces int32 [F,3], vertex_normals float32 [V,3] or None, vertex_colors uint8 [V,3]
+    or None."""
 
     def __init__(self, vertices, faces, vertex_normals, vertex_colors=None):
         self.vertices = vertices
@@ -43,13 +44,15 @@ class Mesh:
         self.vertex_colors = vertex_colors
 
     def numpy(self):
-        """(vertices, faces, vertex_normals, vertex_colors or None) as host arrays."""
+        """(vertices, faces, vertex_normals or None, vertex_colors or None) as host arrays."""
         c = None if self.vertex_colors is None else self.vertex_colors.cpu().numpy()
-        return self.vertices.cpu().numpy(), self.faces.cpu().numpy(), self.vertex_normals.cpu().numpy(), c
+        n = None if self.vertex_normals is None else self.vertex_normals.cpu().numpy()
+        return self.vertices.cpu().numpy(), self.faces.cpu().numpy(), n, c
 
     def export(self, path):
         """Write ``.obj`` (``v x y z [r g b]`` with colour in [0, 1], ``vn``, ``f a//a b//b c//c``, 1-based) or binary little-endian
-        ``.ply`` (float x y z, float nx ny nz, uchar red green blue if coloured; int32 vertex indices)."""
+        ``.ply`` (float x y z, float nx ny nz, uchar red green blue if coloured; int32 vertex indices).  Without normals: no ``vn``
+        lines and ``f a b c`` (OBJ), no normal properties (PLY)."""
         v, f, n, c = self.numpy()
         if str(path).lower().endswith(".obj"):
             with open(path, "w") as fh:
@@ -57,18 +60,26 @@ class Mesh:
                     fh.writelines(f"v {x:.7g} {y:.7g} {z:.7g}\n" for x, y, z in v)
                 else:
                     fh.writelines(f"v {p[0]:.7g} {p[1]:.7g} {p[2]:.7g} {q[0] / 255:.6g} {q[1] / 255:.6g} {q[2] / 255:.6g}\n" for p, q in zip(v, c))
-                fh.writelines(f"vn {x:.7g} {y:.7g} {z:.7g}\n" for x, y, z in n)
-                fh.writelines(f"f {a}//{a} {b}//{b} {d}//{d}\n" for a, b, d in (f.astype(np.int64) + 1))
+                if n is None:
+                    fh.writelines(f"f {a} {b} {d}\n" for a, b, d in (f.astype(np.int64) + 1))
+                else:
+                    fh.writelines(f"vn {x:.7g} {y:.7g} {z:.7g}\n" for x, y, z in n)
+                    fh.writelines(f"f {a}//{a} {b}//{b} {d}//{d}\n" for a, b, d in (f.astype(np.int64) + 1))
         elif str(path).lower().endswith(".ply"):
-            props = ["property float x", "property float y", "property float z", "property float nx", "property float ny", "property float nz"]
-            fields = [("p", "<f4", 3), ("n", "<f4", 3)]
+            props = ["property float x", "property float y", "property float z"]
+            fields = [("p", "<f4", 3)]
+            if n is not None:
+                props += ["property float nx", "property float ny", "property float nz"]
+                fields.append(("n", "<f4", 3))
             if c is not None:
                 props += ["property uchar red", "property uchar green", "property uchar blue"]
                 fields.append(("c", "u1", 3))
             head = "\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + props
                              + [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]) + "\n"
             vert = np.zeros(len(v), dtype=fields)
-            vert["p"], vert["n"] = v, n
+            vert["p"] = v
+            if n is not None:
+                vert["n"] = n
             if c is not None:
                 vert["c"] = c
             face = np.zeros(len(f), dtype=[("k", "u1"), ("i", "<i4", 3)])
@@ -79,6 +90,127 @@ class Mesh:
                 fh.write(face.tobytes())
         else:
             raise ValueError(f"{path}: export writes .obj or .ply")
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _fan(polys):
+    """Triangles (a, b_k, b_{k+1}) from polygons given as lists of vertex indices (k-gons with k >= 3; shorter ones dropped)."""
+    tris = [(p[0], p[k], p[k + 1]) for p in polys for k in range(1, len(p) - 1)]
+    return np.asarray(tris, np.int64).reshape(-1, 3)
+
+
+def _read_obj(path):
+    verts, polys = [], []
+    with open(path) as fh:
+        for line in fh:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "v":
+                verts.append([float(x) for x in t[1:4]])
+            elif t[0] == "f":
+                idx = [int(x.split("/")[0]) for x in t[1:]]
+                polys.append([i - 1 if i > 0 else len(verts) + i for i in idx])      # 1-based; negative = relative
+    return np.asarray(verts, np.float64).reshape(-1, 3), _fan(polys)
+
+
+def _read_ply(path):
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []
+    for line in data[:body].decode("ascii", "replace").splitlines():
+        t = line.split()
+        if not t:
+            continue
+        if t[0] == "format":
+            fmt = t[1]
+        elif t[0] == "element":
+            elements.append((t[1], int(t[2]), []))
+        elif t[0] == "property":
+            if t[1] == "list":
+                elements[-1][2].append((t[4], ("list", _PLY_TYPES[t[2]], _PLY_TYPES[t[3]])))
+            else:
+                elements[-1][2].append((t[2], _PLY_TYPES[t[1]]))
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r}")
+    verts, polys = None, []
+    if fmt == "ascii":
+        words = data[body:].split()
+        pos = 0
+        for name, count, props in elements:
+            rows = []
+            for _ in range(count):
+                row = {}
+                for pname, ptype in props:
+                    if isinstance(ptype, tuple):
+                        k = int(words[pos])
+                        row[pname] = [int(float(w)) for w in words[pos + 1:pos + 1 + k]]
+                        pos += 1 + k
+                    else:
+                        row[pname] = float(words[pos])
+                        pos += 1
+                rows.append(row)
+            if name == "vertex":
+                verts = np.asarray([[r["x"], r["y"], r["z"]] for r in rows], np.float64).reshape(-1, 3)
+            elif name == "face":
+                key = "vertex_indices" if any(p == "vertex_indices" for p, _ in props) else "vertex_index"
+                polys = [r[key] for r in rows]
+    else:
+        e = "<" if fmt == "binary_little_endian" else ">"
+        pos = body
+        for name, count, props in elements:
+            if not any(isinstance(t, tuple) for _, t in props):
+                dt = np.dtype([(pn, e + pt) for pn, pt in props])
+                arr = np.frombuffer(data, dt, count, pos)
+                pos += dt.itemsize * count
+                if name == "vertex":
+                    verts = np.stack([arr["x"], arr["y"], arr["z"]], 1).astype(np.float64)
+                continue
+            rows = []
+            for _ in range(count):           # elements with a list property: one record at a time
+                row = {}
+                for pname, ptype in props:
+                    if isinstance(ptype, tuple):
+                        ct, it = np.dtype(e + ptype[1]), np.dtype(e + ptype[2])
+                        k = int(np.frombuffer(data, ct, 1, pos)[0])
+                        pos += ct.itemsize
+                        row[pname] = np.frombuffer(data, it, k, pos).astype(np.int64).tolist()
+                        pos += it.itemsize * k
+                    else:
+                        pos += np.dtype(ptype).itemsize
+                rows.append(row)
+            if name == "face":
+                key = "vertex_indices" if any(p == "vertex_indices" for p, _ in props) else "vertex_index"
+                polys = [r[key] for r in rows]
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    return verts, _fan(polys)
+
+
+def load_mesh(path, device="cuda:0"):
+    """Read an ``.obj`` (``v`` and ``f`` lines; ``f`` entries as a, a/t, a//n or a/t/n, negative indices relative) or ``.ply``
+    (ascii or binary, any scalar property types, float or double x y z, extra vertex / face properties ignored, face lists with any
+    count and index types) into a device ``Mesh`` (float32 vertices, int32 faces, no normals or colours).  Polygons with more than
+    three vertices are fan-triangulated from their first vertex."""
+    p = str(path).lower()
+    if p.endswith(".obj"):
+        v, f = _read_obj(path)
+    elif p.endswith(".ply"):
+        v, f = _read_ply(path)
+    else:
+        raise ValueError(f"{path}: load_mesh reads .obj or .ply")
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{path}: face index outside the {len(v)} vertices")
+    dev = torch.device(device)
+    return Mesh(torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(f, np.int32)).to(dev), None)
 
 
 def _f12(affine):
