@@ -379,6 +379,47 @@ int vmapstep_clip_box_count(const float* vertices, int64_t n_vertices, const int
 int vmapstep_clip_box_emit(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const float box[15],
                            float* triangles, int64_t n_triangles, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- object bounds (the reference's sceneObject.get_bound, vmap.py:270-315: unproject the keyframes, oriented box) ----------------
+ * vmapstep_unproject_count / _emit: the world points of every pixel of every (object, keyframe) pair whose instance id equals the
+ * pair's id and whose depth is > 0, from a shared frame store: depth float32 [n_slots][width][height], inst int32 (same shape),
+ * t_wc float32 [n_slots][4][4]; intrinsics = (fx, fy, cx, cy).  The point of pixel (w, h) with depth d is
+ * t_wc . ((w - cx) / fx . d, (h - cy) / fy . d, d, 1), float32: xc = ((w - cx) / fx) . d, yc likewise, then
+ * fma(T0, xc, fma(T1, yc, fma(T2, d, T3))) per row.  `pairs` (DEVICE, int32 [n_pairs][2]) = (store slot, instance id), the pairs of
+ * object o being [first_pair[o], first_pair[o + 1]) (`first_pair`: DEVICE int32 [n_obj + 1], `first_pair_host` the same values on the
+ * host, validated: starts at 0, non-decreasing, ends at n_pairs).  A slot outside [0, n_slots) contributes nothing.
+ *   _count enqueues count and scan and writes to DEVICE memory: `offsets` int64 [n_obj + 1] (CSR offsets of the objects' clouds) and
+ *   `bounds` float32 [n_obj][6] (coordinate minimum xyz, maximum xyz of each cloud; +inf / -inf for an empty one); the caller reads
+ *   offsets[n_obj] (the one host synchronisation), allocates and calls
+ *   _emit with the same arguments and workspace: `points` float32 [n_points][3], ordered by (object, pair, pixel index w * height + h);
+ *   nothing is written at or past n_points.  Bit-identical from call to call.
+ * Limits: 1 <= width, height <= 16384, 1 <= n_obj <= 65535, 0 <= n_pairs <= 65535.  Workspace: 256-byte aligned,
+ * >= vmapstep_unproject_workspace_bytes(n_pairs, n_obj, width, height).
+ *
+ * vmapstep_obb_extents: for every object o (points [offsets[o], offsets[o + 1]) of a CSR-segmented cloud, offsets given twice as
+ * for the mesh evaluation) and every candidate k < K with rotation R = rotations[o * set_stride + 9 k ..] (row-major 3 x 3, rows =
+ * box axes; set_stride in floats, 0 = one set shared by all objects, otherwise >= 9 K): lo[o][k][i] / hi[o][k][i] = the minimum /
+ * maximum over the object's points p of fma(R[i][2], q.z, fma(R[i][1], q.y, R[i][0] * q.x)), q = p - center[o] in float32 (`center`:
+ * DEVICE float32 [n_obj][3], NULL = no centring).  An object without points gets lo = +inf, hi = -inf.  Minimum and maximum do not
+ * depend on the order, so the output is bit-identical from call to call and for every `point_chunks` (the number of workgroups an
+ * object's points are spread over; 0 = automatic, at most 65535).  Limits: 1 <= n_obj <= 65535, 1 <= K, n_obj * K * 3 < 2^31.
+ *
+ * vmapstep_cloud_moments: per object the float64 sums of q = p - center[o] and of its products, moments[o] = (x, y, z, xx, xy, xz,
+ * yy, yz, zz), in an order that depends on the object's own points alone (bit-identical whatever else the call holds). */
+int vmapstep_unproject_workspace_bytes(int32_t n_pairs, int32_t n_obj, int32_t width, int32_t height, size_t* bytes);
+int vmapstep_unproject_count(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width, int32_t height,
+                             const float intrinsics[4], const int32_t* pairs, const int32_t* first_pair, const int32_t* first_pair_host,
+                             int32_t n_obj, int32_t n_pairs, int64_t* offsets, float* bounds,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_unproject_emit(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width, int32_t height,
+                            const float intrinsics[4], const int32_t* pairs, const int32_t* first_pair, const int32_t* first_pair_host,
+                            int32_t n_obj, int32_t n_pairs, float* points, int64_t n_points,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_obb_extents(const float* points, int64_t n_points, const int64_t* offsets, const int64_t* offsets_host, int32_t n_obj,
+                         const float* center, const float* rotations, int64_t set_stride, int32_t K, int32_t point_chunks,
+                         float* lo, float* hi, void* stream);
+int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t* offsets, const int64_t* offsets_host, int32_t n_obj,
+                           const float* center, double* moments, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -106,6 +106,8 @@ EXPORTS = (
     "vmapstep_mesh_workspace_bytes", "vmapstep_mesh_grid_points", "vmapstep_mesh_count", "vmapstep_mesh_emit",
     "vmapstep_nn_workspace_bytes", "vmapstep_nn_distance", "vmapstep_surface_sample_workspace_bytes", "vmapstep_surface_sample",
     "vmapstep_clip_box_workspace_bytes", "vmapstep_clip_box_count", "vmapstep_clip_box_emit",
+    "vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
+    "vmapstep_cloud_moments",
 )
 
 _libs = {}
@@ -201,6 +203,19 @@ def load(path=None):
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.vmapstep_clip_box_emit.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_float),
                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _unproject = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float),
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32]
+    lib.vmapstep_unproject_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_unproject_count.argtypes = _unproject + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_unproject_emit.argtypes = _unproject + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_obb_extents.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_cloud_moments.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
+               "vmapstep_cloud_moments"):
+        getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_describe_plan", "vmapstep_param_layout", "vmapstep_workspace_bytes", "vmapstep_fwd_bwd", "vmapstep_render",
                "vmapstep_train_steps", "vmapstep_profile_main_kernel",
                "vmapstep_profile_phases", "vmapstep_prepare", "vmapstep_train_steps_prepared",

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -127,5 +127,42 @@ int clip_box_count(const float* vertices, long long n_vertices, const int* faces
                    void* workspace, hipStream_t st);
 int clip_box_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float box[15], float* triangles,
                   long long n_triangles, void* workspace, hipStream_t st);
+
+// k_bounds.hip: object bounds (bounds_kernels.h).  Unprojection: the workspace holds one int64 per (pair, 1024-pixel block) and the
+// encoded coordinate extremes of every object (uint32 [n_obj][6]).
+struct UnprojectFrames {
+    const float* depth; const int* inst; const float* t_wc;
+    int n_slots, width, height;
+    float fx, fy, cx, cy;
+};
+inline int unproject_blocks(int width, int height) { return (int)(((long long)width * height + 1023) / 1024); }   // = vb::kPixBlock
+struct UnprojectLayout {
+    size_t off_enc, bytes;
+};
+inline UnprojectLayout unproject_layout(int n_pairs, int n_obj, int width, int height) {
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    UnprojectLayout l;
+    l.off_enc = up((size_t)n_pairs * unproject_blocks(width, height) * sizeof(long long)) + 256;
+    l.bytes = l.off_enc + up((size_t)n_obj * 6 * sizeof(unsigned));
+    return l;
+}
+int unproject_count(const UnprojectFrames& f, const int* pairs, const int* first_pair, int n_obj, int n_pairs, long long* offsets,
+                    float* bounds, void* workspace, hipStream_t st);
+int unproject_emit(const UnprojectFrames& f, const int* pairs, const int* first_pair, int n_obj, int n_pairs, float* points,
+                   long long n_points, void* workspace, hipStream_t st);
+// The automatic launch geometry of obb_extents: point chunks per object so that about kObbBlocksTarget workgroups exist (8 per CU),
+// never more than the largest object has 512-point tiles.  The result does not depend on it (minimum and maximum are exact).
+constexpr long long kObbBlocksTarget = 2048;
+inline int obb_chunks(const long long* po, int n_obj, int K) {
+    long long most = 0;
+    for (int o = 0; o < n_obj; ++o) most = po[o + 1] - po[o] > most ? po[o + 1] - po[o] : most;
+    const long long tiles = (most + 511) / 512, per_chunk = (long long)((K + 1023) / 1024) * n_obj;
+    long long c = (kObbBlocksTarget + per_chunk - 1) / per_chunk;
+    c = c > tiles ? tiles : c;
+    return (int)(c < 1 ? 1 : c > 65535 ? 65535 : c);
+}
+int obb_extents(const float* points, const long long* po, int n_obj, const float* center, const float* rotations, long long set_stride,
+                int K, int chunks, float* lo, float* hi, hipStream_t st);
+int cloud_moments(const float* points, const long long* po, int n_obj, const float* center, double* moments, hipStream_t st);
 
 }  // namespace vl

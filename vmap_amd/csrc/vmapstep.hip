@@ -990,6 +990,84 @@ int vmapstep_clip_box_emit(const float* vertices, int64_t n_vertices, const int3
     return vl::clip_box_emit(vertices, n_vertices, faces, n_faces, box, triangles, n_triangles, workspace, static_cast<hipStream_t>(stream));
 }
 
+static int check_unproject(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width, int32_t height,
+                           const float intrinsics[4], const int32_t* pairs, const int32_t* first_pair, const int32_t* first_pair_host,
+                           int32_t n_obj, int32_t n_pairs) {
+    if (n_slots < 1 || width < 1 || height < 1 || width > 16384 || height > 16384 || n_obj < 1 || n_obj > 65535 || n_pairs < 0 || n_pairs > 65535)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "unproject: n_slots=%d width=%d height=%d n_obj=%d n_pairs=%d", n_slots, width, height, n_obj, n_pairs);
+    if (!depth || !inst || !t_wc || !intrinsics || !first_pair || !first_pair_host || (n_pairs > 0 && !pairs))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (!std::isfinite(intrinsics[0]) || !std::isfinite(intrinsics[1]) || !std::isfinite(intrinsics[2]) || !std::isfinite(intrinsics[3]) ||
+        intrinsics[0] == 0.0f || intrinsics[1] == 0.0f)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "unproject: intrinsics must be finite with fx, fy != 0");
+    if (first_pair_host[0] != 0 || first_pair_host[n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "unproject: first_pair must run from 0 to n_pairs");
+    for (int32_t o = 0; o < n_obj; ++o)
+        if (first_pair_host[o + 1] < first_pair_host[o]) return fail(VMAPSTEP_ERR_ARGUMENT, "unproject: first_pair decreases at object %d", (int)o);
+    return VMAPSTEP_OK;
+}
+
+static vl::UnprojectFrames unproject_frames(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width,
+                                            int32_t height, const float k[4]) {
+    return vl::UnprojectFrames{depth, inst, t_wc, n_slots, width, height, k[0], k[1], k[2], k[3]};
+}
+
+int vmapstep_unproject_workspace_bytes(int32_t n_pairs, int32_t n_obj, int32_t width, int32_t height, size_t* bytes) {
+    if (!bytes || n_pairs < 0 || n_pairs > 65535 || n_obj < 1 || n_obj > 65535 || width < 1 || height < 1 || width > 16384 || height > 16384)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "null / negative argument");
+    *bytes = vl::unproject_layout(n_pairs, n_obj, width, height).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_unproject_count(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width, int32_t height,
+                             const float intrinsics[4], const int32_t* pairs, const int32_t* first_pair, const int32_t* first_pair_host,
+                             int32_t n_obj, int32_t n_pairs, int64_t* offsets, float* bounds,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_unproject(depth, inst, t_wc, n_slots, width, height, intrinsics, pairs, first_pair, first_pair_host, n_obj, n_pairs)) return rc;
+    if (!offsets || !bounds) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::unproject_layout(n_pairs, n_obj, width, height).bytes, "unproject")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::unproject_count(unproject_frames(depth, inst, t_wc, n_slots, width, height, intrinsics), pairs, first_pair, n_obj, n_pairs,
+                               reinterpret_cast<long long*>(offsets), bounds, workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_unproject_emit(const float* depth, const int32_t* inst, const float* t_wc, int32_t n_slots, int32_t width, int32_t height,
+                            const float intrinsics[4], const int32_t* pairs, const int32_t* first_pair, const int32_t* first_pair_host,
+                            int32_t n_obj, int32_t n_pairs, float* points, int64_t n_points,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_unproject(depth, inst, t_wc, n_slots, width, height, intrinsics, pairs, first_pair, first_pair_host, n_obj, n_pairs)) return rc;
+    if (n_points < 0 || n_points >= (1ll << 31) || (n_points > 0 && !points)) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument / bad count");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::unproject_layout(n_pairs, n_obj, width, height).bytes, "unproject")) return rc;
+    if (n_points == 0 || n_pairs == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::unproject_emit(unproject_frames(depth, inst, t_wc, n_slots, width, height, intrinsics), pairs, first_pair, n_obj, n_pairs,
+                              points, n_points, workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_obb_extents(const float* points, int64_t n_points, const int64_t* offsets, const int64_t* offsets_host, int32_t n_obj,
+                         const float* center, const float* rotations, int64_t set_stride, int32_t K, int32_t point_chunks,
+                         float* lo, float* hi, void* stream) {
+    if (n_obj < 1 || n_obj > 65535) return fail(VMAPSTEP_ERR_ARGUMENT, "obb extents: n_obj=%d (1 .. 65535)", n_obj);
+    if (K < 1 || (int64_t)n_obj * K * 3 >= (1ll << 31)) return fail(VMAPSTEP_ERR_ARGUMENT, "obb extents: K=%d (K >= 1, n_obj * K * 3 < 2^31)", K);
+    if (set_stride != 0 && set_stride < 9ll * K) return fail(VMAPSTEP_ERR_ARGUMENT, "obb extents: set_stride=%lld (0 or >= 9 K)", (long long)set_stride);
+    if (point_chunks < 0 || point_chunks > 65535) return fail(VMAPSTEP_ERR_ARGUMENT, "obb extents: point_chunks=%d (0 .. 65535)", point_chunks);
+    if (int rc = check_offsets(offsets_host, n_obj, n_points, "obb extents")) return rc;
+    if (!offsets || !rotations || !lo || !hi || (n_points > 0 && !points)) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    const long long* po = reinterpret_cast<const long long*>(offsets_host);
+    const int chunks = point_chunks > 0 ? point_chunks : vl::obb_chunks(po, n_obj, K);
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::obb_extents(points, reinterpret_cast<const long long*>(offsets), n_obj, center, rotations, set_stride, K, chunks, lo, hi,
+                           static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t* offsets, const int64_t* offsets_host, int32_t n_obj,
+                           const float* center, double* moments, void* stream) {
+    if (n_obj < 1 || n_obj > 65535) return fail(VMAPSTEP_ERR_ARGUMENT, "cloud moments: n_obj=%d (1 .. 65535)", n_obj);
+    if (int rc = check_offsets(offsets_host, n_obj, n_points, "cloud moments")) return rc;
+    if (!offsets || !moments || (n_points > 0 && !points)) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::cloud_moments(points, reinterpret_cast<const long long*>(offsets), n_obj, center, moments, static_cast<hipStream_t>(stream));
+}
+
 static_assert(sizeof(vmapstep_sample_object) == sizeof(vs::SampleObject), "sample object table layout");
 
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {

@@ -124,3 +124,11 @@ class ObjectKeyframes:
         last2 = (self.latest + [0, 0])[:2] if len(self.latest) < 2 else self.latest[-2:]
         return dict(store=self.store, slots=self._slots_dev, bbox=self.bbox, n_keyframes=self.n_keyframes,
                     last2=tuple(int(v) for v in last2), center=self.center, obj_id=self.obj_id)
+
+    # ---- the object's 3-D box (sceneObject.get_bound, vmap.py:270-315) -----------------------------------------
+    def get_bound(self, intrinsics):
+        """The oriented box of everything this object's keyframes see of it (``bounds.get_bounds`` for one object): a
+        ``meshing.BoundingBox`` for ``Trainer.meshing``, or ``None`` (fewer than 4 points, or a flat cloud).  ``intrinsics``:
+        (fx, fy, cx, cy), a 3 x 3 matrix or an object with those attributes."""
+        from . import bounds
+        return bounds.get_bounds([self], intrinsics)[0]
