@@ -75,6 +75,26 @@ def test_object_points_match_the_checker(scene):
     assert objs[2].get_bound(scene.k4) is None
 
 
+@pytest.mark.parametrize("n_objects", [1, 2])
+def test_object_points_match_the_checker_past_one_scan_chunk(n_objects):
+    """Two keyframes of 1200 x 680 are 797 blocks each: one object has 1594 block totals, two have 3188, so unproject_scan leaves its
+    first chunk of 1024 inside an object (and between objects).  Point by point against the checker, with the small scene's bound."""
+    bounds, _ = _mods()
+    big = bo.Scene(width=1200, height=680, fx=1000.0, n_views=2, radius=3.0, seed=2)
+    _, objs = _store_scene(big)
+    pts, off = bounds.object_points(objs[:n_objects], big.k4)
+    pts = pts.cpu().numpy()
+    assert off[0] == 0 and off[-1] == len(pts) and len(off) == n_objects + 1
+    for o, b in enumerate(big.boxes[:n_objects]):
+        ref, scale = big.cloud(b["id"])
+        got = pts[off[o]:off[o + 1]]
+        assert len(got) == len(ref) > 100_000
+        err = np.abs(got.astype(np.float64) - ref)
+        bound = 6 * 2.0 ** -24 * scale
+        print(f"id {b['id']}: {len(ref)} points, worst error / bound {float((err / bound).max()):.3f}")
+        assert np.all(err <= bound)
+
+
 def _clouds(rng, sizes):
     parts = [(rng.standard_normal((n, 3)) * rng.uniform(0.05, 30.0) * (1.0, 2.0, 0.3) + rng.uniform(-3, 3, 3)).astype(np.float32) for n in sizes]
     return parts, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)

@@ -136,6 +136,35 @@ def test_nn_segmented_batch_equals_single_calls_and_is_deterministic():
         _check_nn(q[qo[s]:qo[s + 1]], r[ro[s]:ro[s + 1]], d[qo[s]:qo[s + 1]], i[qo[s]:qo[s + 1]] - ro[s])
 
 
+def test_nn_over_more_sets_than_one_plan_chunk_equals_single_calls():
+    """1025 small sets, some without queries or without anything: nn_plan's prefix of the work items leaves its first chunk of 1024
+    sets, and nn_search finds the set of every item in it.  Against the same call made set by set, bit for bit."""
+    rng = np.random.default_rng(31)
+    ev = _ev()
+    n_sets = 1025
+    qs = rng.integers(1, 40, n_sets)
+    rs = rng.integers(1, 30, n_sets)
+    empty = rng.random(n_sets) < 0.2
+    empty[[0, 511, 1023]] = True                                   # an empty set first and on both sides of the chunk's edge
+    empty[[1, 1022, 1024]] = False
+    qs[empty] = 0
+    rs[empty & (rng.random(n_sets) < 0.5)] = 0                     # refs without queries, or nothing at all
+    q = _cloud("random", int(qs.sum()), rng, 3.0)
+    r = _cloud("random", int(rs.sum()), rng, 3.0)
+    d, i = ev.nn_distance(q, r, qs, rs, return_index=True)
+    d, i = d.cpu().numpy(), i.cpu().numpy()
+    qo, ro = np.concatenate([[0], np.cumsum(qs)]), np.concatenate([[0], np.cumsum(rs)])
+    assert (qs[1024] > 0) and len(d) == qo[-1]
+    for s in range(n_sets):
+        if qs[s] == 0:
+            continue
+        ds, is_ = ev.nn_distance(q[qo[s]:qo[s + 1]], r[ro[s]:ro[s + 1]], return_index=True)
+        np.testing.assert_array_equal(d[qo[s]:qo[s + 1]], ds.cpu().numpy(), err_msg=f"set {s}")
+        np.testing.assert_array_equal(i[qo[s]:qo[s + 1]], is_.cpu().numpy() + ro[s], err_msg=f"set {s}")
+    for s in (1, 1022, 1024):
+        _check_nn(q[qo[s]:qo[s + 1]], r[ro[s]:ro[s + 1]], d[qo[s]:qo[s + 1]], i[qo[s]:qo[s + 1]] - ro[s])
+
+
 def test_nn_writes_only_its_query_range():
     rng = np.random.default_rng(4)
     ev = _ev()
@@ -267,6 +296,35 @@ def test_clip_matches_the_float64_clipper():
     # everything outside: None; and determinism
     assert ev.crop_to_box(m, BoundingBox(center=[40, 40, 40], R=np.eye(3), extent=[1, 1, 1])) is None
     assert torch.equal(ev.crop_to_box(m, box).vertices, got.vertices)
+
+
+@pytest.mark.parametrize("nblk", [1023, 1024, 1025, 2049])
+def test_clip_of_whole_triangles_across_scan_chunks(nblk):
+    """``nblk`` blocks of 256 faces (the last one partial), so that clip_scan ends on, at and past its chunks of 1024 block totals.
+    Every triangle lies wholly inside the box or wholly beyond one of its planes, so the crop is v[f[inside]] bit for bit, in face
+    order.  Runs of whole blocks keep nothing: totals of zero inside the scan."""
+    rng = np.random.default_rng(nblk)
+    ev = _ev()
+    from vmap_amd.meshing import BoundingBox, Mesh
+    nf = 256 * nblk - 5
+    R = _rotation(rng)
+    centre, extent = np.array([4.1, 3.9, 4.2]), np.array([1.8, 1.2, 2.0])
+    inside = rng.random(nf) < 0.5
+    inside[256 * 3:256 * 7] = False
+    inside[256 * (nblk - 4):256 * (nblk - 2)] = False
+    inside[[0, nf - 1]] = True
+    # local centres: inside at least 0.1 from every plane, outside at least 0.1 beyond the +- plane of one axis; triangles of 0.02
+    loc = rng.uniform(-1, 1, (nf, 3)) * (extent / 2 - 0.1)
+    ax = rng.integers(0, 3, nf)
+    out = ~inside
+    loc[out, ax[out]] = (rng.choice([-1.0, 1.0], out.sum()) * (extent[ax[out]] / 2 + 0.1 + rng.uniform(0, 1, out.sum())))
+    v = ((loc @ R.T + centre)[:, None, :] + rng.uniform(-0.02, 0.02, (nf, 3, 3))).reshape(-1, 3).astype(np.float32)
+    f = np.arange(3 * nf, dtype=np.int32).reshape(-1, 3)
+    f = f[:, rng.permutation(3)]
+    got = ev.crop_to_box(Mesh(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), None), BoundingBox(center=centre, R=R, extent=extent))
+    assert got.faces.shape[0] == inside.sum()
+    np.testing.assert_array_equal(got.vertices.cpu().numpy().reshape(-1, 3, 3), v[f[inside]])
+    np.testing.assert_array_equal(got.faces.cpu().numpy(), np.arange(3 * inside.sum(), dtype=np.int32).reshape(-1, 3))
 
 
 def _sphere_mesh(r, grid=256, center=(0.0, 0.0, 0.0)):

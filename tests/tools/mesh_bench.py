@@ -24,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from vmap_amd import _lib, meshing  # noqa: E402
+from vmap_amd import _devmem, _lib, meshing  # noqa: E402
 from vmap_amd.trainer import SimpleConfig, Trainer  # noqa: E402
 
 HBM_ACHIEVABLE = 6.3e12
@@ -47,8 +47,8 @@ def mesh_stages(vol, reps):
     """count / readback / emit of one volume through the C ABI."""
     lib = _lib.load()
     shape = tuple(vol.shape)
-    ws, ws_ptr, nbytes = meshing._workspace(shape, vol.device)
-    stream = torch.cuda.current_stream().cuda_stream
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_mesh_workspace_bytes, vol.device, *shape)
+    stream = _devmem.stream(vol.device)
     counts = torch.empty(2, dtype=torch.int64, device=vol.device)
     host = torch.empty(2, dtype=torch.int64).pin_memory()
 

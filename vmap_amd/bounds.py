@@ -45,7 +45,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _devmem, _lib
 from .meshing import BoundingBox
 
 __all__ = ["object_points", "oriented_bounds", "get_bounds", "coarse_rotations", "extents",
@@ -77,15 +77,6 @@ def _intrinsics4(intrinsics):
     raise _lib.VmapStepError("intrinsics: (fx, fy, cx, cy), a 3 x 3 matrix or an object with fx, fy, cx, cy")
 
 
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _aligned(nbytes, device):
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
-
-
 def _object_points(objects, intrinsics):
     """(points float32 [N, 3] on the store's device, host offsets int64 [n_obj + 1], bounds float32 [n_obj, 6] on the device)."""
     objects = list(objects)
@@ -110,20 +101,18 @@ def _object_points(objects, intrinsics):
     depth, inst, t_wc = store.depth, store.inst, store.t_wc
     if not (depth.is_contiguous() and inst.is_contiguous() and t_wc.is_contiguous()):
         raise _lib.VmapStepError("object_points: the FrameStore tensors must be contiguous")
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.vmapstep_unproject_workspace_bytes(n_pairs, n_obj, store.W, store.H, ctypes.byref(nb)), lib)
-    ws, ws_ptr = _aligned(nb.value, dev)
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_unproject_workspace_bytes, dev, n_pairs, n_obj, store.W, store.H)
     offsets = torch.empty(n_obj + 1, dtype=torch.int64, device=dev)
     bounds = torch.empty(n_obj, 6, dtype=torch.float32, device=dev)
     head = (depth.data_ptr(), inst.data_ptr(), t_wc.data_ptr(), store.capacity, store.W, store.H, k4, pairs_d.data_ptr(), first_d.data_ptr(),
             first_h.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_obj, n_pairs)
     with torch.cuda.device(dev):
-        stream = _stream(dev)
-        _lib.check(lib.vmapstep_unproject_count(*head, offsets.data_ptr(), bounds.data_ptr(), ws_ptr, nb.value, stream), lib)
+        stream = _devmem.stream(dev)
+        _lib.check(lib.vmapstep_unproject_count(*head, offsets.data_ptr(), bounds.data_ptr(), ws_ptr, nbytes, stream), lib)
         off_h = offsets.cpu().numpy()               # the one host synchronisation
         n = int(off_h[-1])
         points = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        _lib.check(lib.vmapstep_unproject_emit(*head, points.data_ptr(), n, ws_ptr, nb.value, stream), lib)
+        _lib.check(lib.vmapstep_unproject_emit(*head, points.data_ptr(), n, ws_ptr, nbytes, stream), lib)
     del ws
     return points, off_h, bounds
 
@@ -217,7 +206,7 @@ class _HipBackend:
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.vmapstep_obb_extents(self.points.data_ptr(), len(self.points), self.off_d.data_ptr(), self._off_p(), self.n_obj,
                                                      None if c is None else c.data_ptr(), rot.data_ptr(), 0 if shared else 9 * K, K,
-                                                     self.point_chunks, lo.data_ptr(), hi.data_ptr(), _stream(self.dev)), self.lib)
+                                                     self.point_chunks, lo.data_ptr(), hi.data_ptr(), _devmem.stream(self.dev)), self.lib)
         return lo, hi
 
     def moments(self, center):
@@ -225,7 +214,7 @@ class _HipBackend:
         out = torch.empty(self.n_obj, 9, dtype=torch.float64, device=self.dev)
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.vmapstep_cloud_moments(self.points.data_ptr(), len(self.points), self.off_d.data_ptr(), self._off_p(), self.n_obj,
-                                                       c.data_ptr(), out.data_ptr(), _stream(self.dev)), self.lib)
+                                                       c.data_ptr(), out.data_ptr(), _devmem.stream(self.dev)), self.lib)
         return out.cpu().numpy()
 
 

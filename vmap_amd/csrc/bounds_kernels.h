@@ -9,6 +9,8 @@
 //                                   the object's by an integer atomic min / max of the order-preserving encoding
 //                  unproject_scan   one workgroup: exclusive scan of the block totals; the per-object offsets and decoded bounds
 //                  unproject_emit   per block again: block scan + block offset -> each pixel's output row; the same point function
+//                                   (the block scans and the scan of the totals are scan_ops.h's: wave shuffles, one LDS word per
+//                                   wave; a pair's object is the segment of the pair in first_pair)
 //   box search     obb_init         lo = enc(+inf), hi = enc(-inf) for every (object, candidate, axis)
 //                  obb_extents      the hot kernel.  A block = (1024 candidates, one chunk of one object's points).  Lanes own
 //                                   candidates: kObbCand per lane, each 9 rotation entries and 6 running extremes in registers.  The
@@ -24,15 +26,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace vb {
+#include "launch_geometry.h"
+#include "scan_ops.h"
 
-constexpr int kBoundsWG = 256;             // unproject_count / _emit, obb_extents, the elementwise kernels
-constexpr int kPixPer = 4;                 // consecutive pixels per lane of unproject_count / _emit
-constexpr int kPixBlock = kBoundsWG * kPixPer;
-constexpr int kScanWG = 1024;              // unproject_scan, cloud_moments
-constexpr int kObbCand = 4;                // candidates per lane
-constexpr int kObbBlock = kBoundsWG * kObbCand;   // candidates per block
-constexpr int kObbTile = 512;              // points per LDS tile (float4 each: 8 KiB)
+namespace vb {
 
 __device__ __forceinline__ unsigned enc_f32(float v) {
     const unsigned b = __float_as_uint(v);
@@ -40,25 +37,6 @@ __device__ __forceinline__ unsigned enc_f32(float v) {
 }
 __device__ __forceinline__ float dec_f32(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// inclusive scan of one value per lane over a workgroup of WG lanes (Hillis-Steele in LDS); every lane gets the total as well
-template <int WG, typename T>
-__device__ __forceinline__ T block_inclusive_scan(T v, T* lds, T& total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < WG; off <<= 1) {
-        const T add = t >= off ? lds[t - off] : T(0);
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const T out = lds[t];
-    total = lds[WG - 1];
-    __syncthreads();
-    return out;
 }
 
 // ---- unprojection (vmap.py:272-282: Open3D's float-image path, no depth scale, no truncation) -------------------------------------
@@ -116,17 +94,18 @@ __global__ void __launch_bounds__(kBoundsWG) unproject_init(UnprojArgs a) {
 }
 
 __global__ void __launch_bounds__(kBoundsWG) unproject_count(UnprojArgs a) {
-    __shared__ long long lds[kBoundsWG];
+    __shared__ int wsum[kBoundsWG / 64];
     __shared__ unsigned ext[6];
     const int pair = blockIdx.y;
     const long long pix0 = ((long long)blockIdx.x * kBoundsWG + threadIdx.x) * kPixPer;
     if (threadIdx.x < 6) ext[threadIdx.x] = enc_f32(threadIdx.x < 3 ? __builtin_inff() : -__builtin_inff());
     float d[kPixPer];
     const int mask = unproject_lane(a, pair, pix0, d);
-    long long total;
-    (void)block_inclusive_scan<kBoundsWG>((long long)__builtin_popcount(mask), lds, total);      // its barriers publish ext[]
+    int total;                                 // at most kPixBlock
+    (void)vscan::wg_exclusive_scan<kBoundsWG>(__builtin_popcount(mask), wsum, total);
     if (threadIdx.x == 0) a.blk[(long long)pair * a.nb + blockIdx.x] = total;
-    if (total == 0) return;
+    if (total == 0) return;                    // uniform over the block
+    __syncthreads();                           // ext[] is initialised before any lane's atomics reach it
     if (mask) {
         const float* T = a.t_wc + 16 * (long long)a.pairs[2 * pair];
         const float inf = __builtin_inff();
@@ -147,29 +126,17 @@ __global__ void __launch_bounds__(kBoundsWG) unproject_count(UnprojArgs a) {
     }
     __syncthreads();
     if (threadIdx.x < 6) {
-        int lo_o = 0, hi_o = a.n_obj;      // the object of this pair: the last o with first_pair[o] <= pair
-        while (hi_o - lo_o > 1) {
-            const int mid = (lo_o + hi_o) >> 1;
-            if (a.first_pair[mid] <= pair) lo_o = mid; else hi_o = mid;
-        }
-        unsigned* e = a.enc + 6 * lo_o + threadIdx.x;
+        unsigned* e = a.enc + 6 * vscan::segment_of(a.first_pair, a.n_obj, pair) + threadIdx.x;      // the object of this pair
         if (threadIdx.x < 3) atomicMin(e, ext[threadIdx.x]); else atomicMax(e, ext[threadIdx.x]);
     }
 }
 
 __global__ void __launch_bounds__(kScanWG) unproject_scan(UnprojArgs a) {
-    __shared__ long long lds[kScanWG];
+    __shared__ long long wsum[kScanWG / 64];
     const long long n = (long long)a.n_pairs * a.nb;
-    long long carry = 0;
-    for (long long base = 0; base < n; base += kScanWG) {
-        const long long b = base + threadIdx.x;
-        const long long v = b < n ? a.blk[b] : 0;
-        long long total;
-        const long long incl = block_inclusive_scan<kScanWG>(v, lds, total);
-        if (b < n) a.blk[b] = carry + incl - v;
-        carry += total;
-    }
-    __syncthreads();
+    const long long carry = vscan::wg_scan_totals<kScanWG>(
+        n, wsum, [&](long long b) { return a.blk[b]; }, [&](long long b, long long ex) { a.blk[b] = ex; });
+    __syncthreads();                           // the offsets below read prefixes other lanes stored
     for (int o = threadIdx.x; o <= a.n_obj; o += kScanWG) {
         const long long b = (long long)a.first_pair[o] * a.nb;
         a.offsets[o] = b < n ? a.blk[b] : carry;
@@ -178,14 +145,13 @@ __global__ void __launch_bounds__(kScanWG) unproject_scan(UnprojArgs a) {
 }
 
 __global__ void __launch_bounds__(kBoundsWG) unproject_emit(UnprojArgs a) {
-    __shared__ long long lds[kBoundsWG];
+    __shared__ int wsum[kBoundsWG / 64];
     const int pair = blockIdx.y;
     const long long pix0 = ((long long)blockIdx.x * kBoundsWG + threadIdx.x) * kPixPer;
     float d[kPixPer];
     const int mask = unproject_lane(a, pair, pix0, d);
-    const long long t = __builtin_popcount(mask);
-    long long total;
-    long long o = a.blk[(long long)pair * a.nb + blockIdx.x] + block_inclusive_scan<kBoundsWG>(t, lds, total) - t;
+    int total;
+    long long o = a.blk[(long long)pair * a.nb + blockIdx.x] + vscan::wg_exclusive_scan<kBoundsWG>(__builtin_popcount(mask), wsum, total);
     if (!mask) return;
     const float* T = a.t_wc + 16 * (long long)a.pairs[2 * pair];
 #pragma unroll

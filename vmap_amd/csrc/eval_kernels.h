@@ -4,33 +4,33 @@
 // Three families, none of which lets the dispatch order decide a result (the output is bit-identical from call to call and does
 // not depend on the launch geometry):
 //   nearest neighbour  nn_plan     one workgroup: per set, (query blocks x ref chunks) work items, exclusive prefix to the workspace
+//                                  (scan_ops.h's scan of totals)
 //                      nn_init     the packed (squared distance bits, ref index) key of every query = all ones
-//                      nn_search   one item per workgroup: kNnQ queries per lane in registers, the item's refs staged through LDS
+//                      nn_search   one item per workgroup (its set: the segment of the item in that prefix): kNnQ queries per lane in registers, the item's refs staged through LDS
 //                                  kNnTile at a time and broadcast to the wave; per query the running (min, first index), then one
 //                                  64-bit atomic min of the packed key.  A squared distance is >= 0, so its float bits order as the
 //                                  value; the low word breaks ties to the smallest ref index; min is order-independent
 //                      nn_finalize dist = sqrtf(min squared distance), index = the key's low word
-//   surface sampling   surface_cdf     one workgroup per set: float64 face areas, inclusive per-set cumulative sum
+//   surface sampling   surface_cdf     one workgroup per set: float64 face areas, inclusive per-set cumulative sum (a scan of its
+//                                      own, in a fixed order of additions)
 //                      surface_sample  per point: u0 -> searchsorted_left(cdf, u0 * total), (r1, r2) folded, v0 + r1 e1 + r2 e2
 //   box clipping       clip_count  per face: triangles left after Sutherland-Hodgman against the box's 6 half-spaces; per-block
 //                                  totals to the workspace
 //                      clip_scan   one workgroup: exclusive scan of the block totals, the grand total to a device int64
 //                      clip_emit   per face again: block scan + block offset -> its first output triangle; the fan from vertex 0
+//                                  (the block scans and the scan of the totals are scan_ops.h's: wave shuffles, one LDS word per wave)
 // Distances are always taken from coordinate differences (dx*dx + dy*dy + dz*dz), never from |a|^2 + |b|^2 - 2 a.b, which loses
 // millimetres at room scale exactly where the completion ratio at 1 cm is decided.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "launch_geometry.h"
+#include "scan_ops.h"
+
 namespace ve {
 
-constexpr int kNnWG = 256;                 // lanes per nn_search workgroup
-constexpr int kNnQ = 8;                    // queries per lane
-constexpr int kNnQB = kNnWG * kNnQ;        // queries per work item
-constexpr int kNnTile = 512;               // refs per LDS tile (float4 each: 8 KiB)
-constexpr int kPlanWG = 1024;              // nn_plan, clip_scan
 constexpr int kCdfWG = 256;                // surface_cdf
 constexpr int kCdfPer = 4;                 // faces per lane and round of surface_cdf
-constexpr int kEvalWG = 256;               // the elementwise kernels, clip_count / clip_emit
 
 struct NnArgs {
     const float* q;                        // [n][3]
@@ -52,37 +52,11 @@ __device__ __forceinline__ long long nn_items(const NnArgs& a, int s) {
     return ((nq + kNnQB - 1) / kNnQB) * ((nr + a.rchunk - 1) / a.rchunk);
 }
 
-// inclusive scan of one value per lane over a workgroup of WG lanes (Hillis-Steele in LDS); every lane gets the total as well
-template <int WG, typename T>
-__device__ __forceinline__ T block_inclusive_scan(T v, T* lds, T& total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < WG; off <<= 1) {
-        const T add = t >= off ? lds[t - off] : T(0);
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const T out = lds[t];
-    total = lds[WG - 1];
-    __syncthreads();
-    return out;
-}
-
 __global__ void __launch_bounds__(kPlanWG) nn_plan(NnArgs a) {
-    __shared__ long long lds[kPlanWG];
-    long long carry = 0;
-    for (int base = 0; base < a.n_sets; base += kPlanWG) {
-        const int s = base + (int)threadIdx.x;
-        const long long n = s < a.n_sets ? nn_items(a, s) : 0;
-        long long total;
-        const long long incl = block_inclusive_scan<kPlanWG>(n, lds, total);
-        if (s < a.n_sets) a.prefix[s] = carry + incl - n;
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.prefix[a.n_sets] = carry;
+    __shared__ long long wsum[kPlanWG / 64];
+    const long long items = vscan::wg_scan_totals<kPlanWG>(
+        a.n_sets, wsum, [&](long long s) { return nn_items(a, (int)s); }, [&](long long s, long long ex) { a.prefix[s] = ex; });
+    if (threadIdx.x == 0) a.prefix[a.n_sets] = items;
 }
 
 __global__ void __launch_bounds__(kEvalWG) nn_init(NnArgs a) {
@@ -93,13 +67,7 @@ __global__ void __launch_bounds__(kEvalWG) nn_init(NnArgs a) {
 __global__ void __launch_bounds__(kNnWG) nn_search(NnArgs a) {
     __shared__ float4 tile[kNnTile];
     const long long item = blockIdx.x;
-    // the set of this item: the last s with prefix[s] <= item (sets without items share their successor's prefix)
-    int lo = 0, hi = a.n_sets;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.prefix[mid] <= item) lo = mid; else hi = mid;
-    }
-    const int s = lo;
+    const int s = vscan::segment_of(a.prefix, a.n_sets, item);      // sets without items share their successor's prefix
     const long long q0 = a.qo[s], q1 = a.qo[s + 1], r0 = a.ro[s], r1 = a.ro[s + 1];
     const long long nrc = (r1 - r0 + a.rchunk - 1) / a.rchunk;
     const long long local = item - a.prefix[s];
@@ -211,6 +179,25 @@ __device__ __forceinline__ double face_area(const SurfArgs& a, long long face) {
     return 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
 }
 
+// Inclusive scan of one float64 per lane over the kCdfWG lanes (Hillis-Steele in LDS); every lane gets the total as well.  Not
+// scan_ops.h's shuffle scan: this tree fixes the order of the float64 additions, and the cumulative areas decide a sample's face.
+__device__ __forceinline__ double cdf_inclusive_scan(double v, double* lds, double& total) {
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int off = 1; off < kCdfWG; off <<= 1) {
+        const double add = t >= off ? lds[t - off] : 0.0;
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const double out = lds[t];
+    total = lds[kCdfWG - 1];
+    __syncthreads();
+    return out;
+}
+
 __global__ void __launch_bounds__(kCdfWG) surface_cdf(SurfArgs a) {
     __shared__ double lds[kCdfWG];
     const int s = blockIdx.x;
@@ -226,7 +213,7 @@ __global__ void __launch_bounds__(kCdfWG) surface_cdf(SurfArgs a) {
             part[c] = sum;
         }
         double total;
-        const double incl = block_inclusive_scan<kCdfWG>(sum, lds, total);
+        const double incl = cdf_inclusive_scan(sum, lds, total);
         const double excl = carry + (incl - sum);
 #pragma unroll
         for (int c = 0; c < kCdfPer; ++c)
@@ -238,13 +225,7 @@ __global__ void __launch_bounds__(kCdfWG) surface_cdf(SurfArgs a) {
 __global__ void __launch_bounds__(kEvalWG) surface_sample(SurfArgs a) {
     const long long j = a.o_begin + (long long)blockIdx.x * kEvalWG + threadIdx.x;
     if (j >= a.o_end) return;
-    // the set of point j: the last s with oo[s] <= j (empty sets share their successor's offset)
-    int lo = 0, hi = a.n_sets;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.oo[mid] <= j) lo = mid; else hi = mid;
-    }
-    const int s = lo;
+    const int s = vscan::segment_of(a.oo, a.n_sets, j);             // the set of point j
     double u0;
     float r1, r2;
     if (a.u0) {
@@ -332,42 +313,35 @@ __device__ __forceinline__ int clip_face(const ClipArgs& a, long long face, floa
 }
 
 __global__ void __launch_bounds__(kEvalWG) clip_count(ClipArgs a) {
-    __shared__ long long lds[kEvalWG];
+    __shared__ int wsum[kEvalWG / 64];
     const long long face = (long long)blockIdx.x * kEvalWG + threadIdx.x;
-    long long t = 0;
+    int t = 0;                                 // at most kClipMax - 2 per face: a block's sums fit an int
     if (face < a.n_faces) {
         float px[kClipMax], py[kClipMax], pz[kClipMax];
         const int n = clip_face(a, face, px, py, pz);
         t = n >= 3 ? n - 2 : 0;
     }
-    long long total;
-    (void)block_inclusive_scan<kEvalWG>(t, lds, total);
+    int total;
+    (void)vscan::wg_exclusive_scan<kEvalWG>(t, wsum, total);
     if (threadIdx.x == 0) a.blk[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(kPlanWG) clip_scan(ClipArgs a) {
-    __shared__ long long lds[kPlanWG];
-    long long carry = 0;
-    for (int base = 0; base < a.nblk; base += kPlanWG) {
-        const int b = base + (int)threadIdx.x;
-        const long long n = b < a.nblk ? a.blk[b] : 0;
-        long long total;
-        const long long incl = block_inclusive_scan<kPlanWG>(n, lds, total);
-        if (b < a.nblk) a.blk[b] = carry + incl - n;
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.count[0] = carry;
+    __shared__ long long wsum[kPlanWG / 64];
+    const long long all = vscan::wg_scan_totals<kPlanWG>(
+        a.nblk, wsum, [&](long long b) { return a.blk[b]; }, [&](long long b, long long ex) { a.blk[b] = ex; });
+    if (threadIdx.x == 0) a.count[0] = all;
 }
 
 __global__ void __launch_bounds__(kEvalWG) clip_emit(ClipArgs a) {
-    __shared__ long long lds[kEvalWG];
+    __shared__ int wsum[kEvalWG / 64];
     const long long face = (long long)blockIdx.x * kEvalWG + threadIdx.x;
     float px[kClipMax], py[kClipMax], pz[kClipMax];
     int n = 0;
     if (face < a.n_faces) n = clip_face(a, face, px, py, pz);
-    const long long t = n >= 3 ? n - 2 : 0;
-    long long total;
-    const long long first = a.blk[blockIdx.x] + block_inclusive_scan<kEvalWG>(t, lds, total) - t;
+    const int t = n >= 3 ? n - 2 : 0;
+    int total;
+    const long long first = a.blk[blockIdx.x] + vscan::wg_exclusive_scan<kEvalWG>(t, wsum, total);
     for (int k = 0; k < t; ++k) {
         const long long o = first + k;
         if (o >= a.cap) break;

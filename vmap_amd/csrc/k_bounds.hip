@@ -8,9 +8,6 @@
 
 namespace vl {
 
-static_assert(vb::kPixBlock == 1024, "unproject_blocks (launch.h) assumes 1024 pixels per workgroup");
-static_assert(vb::kObbBlock == 1024 && vb::kObbTile == 512, "obb_chunks (launch.h) assumes 1024 candidates per workgroup, 512-point tiles");
-
 static vb::UnprojArgs unproject_args(const UnprojectFrames& f, const int* pairs, const int* first_pair, int n_obj, int n_pairs, void* workspace) {
     vb::UnprojArgs a;
     std::memset(&a, 0, sizeof(a));

@@ -8,9 +8,6 @@
 
 namespace vl {
 
-static_assert(ve::kNnQB == 2048 && ve::kNnTile == 512, "nn_plan_host (launch.h) assumes 2048 queries per item, 512-ref tiles");
-static_assert(ve::kEvalWG == 256, "clip_box_bytes (launch.h) assumes 256 faces per workgroup");
-
 static int grid_of(long long n) { return (int)((n + ve::kEvalWG - 1) / ve::kEvalWG); }
 
 int nn_distance(const NnPlan& p, const float* queries, const long long* qo, const float* refs, const long long* ro, int n_sets,

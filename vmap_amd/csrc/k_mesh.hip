@@ -8,8 +8,6 @@
 
 namespace vl {
 
-static_assert(vm::kMeshWG == 256, "mesh_layout (launch.h) assumes 256 points per workgroup");
-
 static vm::MeshArgs mesh_args(const float* volume, int nx, int ny, int nz, float level, void* workspace) {
     const MeshLayout l = mesh_layout(nx, ny, nz);
     vm::MeshArgs a;

@@ -5,18 +5,20 @@
 // so the output is bit-identical from call to call and independent of dispatch order):
 //   mesh_count          per grid point: which of its three +axis edges cross the level (it owns them) and, for the cell whose lowest
 //                       corner it is, the triangle count of the cell's cube index; per-workgroup totals to the workspace
-//   mesh_scan           one workgroup: exclusive scan of the workgroup totals, grand totals (vertices, faces) to a device int64[2]
+//   mesh_scan           one workgroup: exclusive scan of the workgroup totals (both columns in one pass), grand totals (vertices,
+//                       faces) to a device int64[2]
 //   mesh_emit_vertices  workgroup scan + workgroup offset -> the vertex id of every crossing edge; position and normal written
 //   mesh_emit_faces     workgroup scan + workgroup offset -> face ids; the classic table's triangles as the owners' vertex ids
 // Output order: vertices by owning point (i * ny + j) * nz + k, then axis 0, 1, 2; faces by cell (= its lowest corner's index),
-// then table order.  Every kernel handles one grid point per thread, kMeshWG points per workgroup.
+// then table order.  Every kernel handles one grid point per thread, kMeshWG points per workgroup.  The workgroup scans and the scan
+// of the totals are scan_ops.h's (wave shuffles, one LDS word per wave).
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace vm {
+#include "launch_geometry.h"
+#include "scan_ops.h"
 
-constexpr int kMeshWG = 256;        // points per workgroup of count / emit
-constexpr int kScanWG = 1024;       // the single workgroup of mesh_scan
+namespace vm {
 
 // The classic (Lorensen) triangle table: for each cube index (bit c set iff corner c lies strictly above the level), up to five
 // triangles as edge ids, -1 terminated.  Corners and edges are numbered as in Lorensen & Cline / Bourke's table with x along the
@@ -328,28 +330,6 @@ __device__ __forceinline__ void decode(int p, const MeshArgs& a, int& i, int& j,
     i = r / a.ny;
 }
 
-// Exclusive scan of one int per thread over the workgroup (kMeshWG = 4 waves of 64); *total = the workgroup's sum.
-__device__ __forceinline__ int wg_exclusive_scan(int x, int* lds4, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(s, d, 64);
-        if (lane >= d) s += y;
-    }
-    if (lane == 63) lds4[wave] = s;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kMeshWG / 64; ++w) {
-        const int t = lds4[w];
-        before += w < wave ? t : 0;
-        sum += t;
-    }
-    *total = sum;
-    return before + s - x;
-}
-
 __device__ __forceinline__ unsigned cube_index(const MeshArgs& a, int p) {
     const int si = a.ny * a.nz, sj = a.nz;
     const float* v = a.vol + p;
@@ -388,52 +368,29 @@ __global__ __launch_bounds__(kMeshWG) void mesh_count(const MeshArgs a) {
         nv = __popc(m);
         if (owns_cell(a, i, j, k)) nf = tri_count(cube_index(a, p));
     }
-    int tv, tf;
-    wg_exclusive_scan(nv, lds4[0], &tv);
-    wg_exclusive_scan(nf, lds4[1], &tf);
+    int tv, tf;                        // two scans in a row: an LDS array each (scan_ops.h's barrier contract)
+    vscan::wg_exclusive_scan<kMeshWG>(nv, lds4[0], tv);
+    vscan::wg_exclusive_scan<kMeshWG>(nf, lds4[1], tf);
     if (threadIdx.x == 0) {
         a.blk[2 * blockIdx.x] = tv;
         a.blk[2 * blockIdx.x + 1] = tf;
     }
 }
 
-// One workgroup: the per-workgroup totals -> exclusive offsets (in place), grand totals -> counts.  Vertices in the low and faces in
-// the high half of one 64-bit word per workgroup (a kScanWG-chunk's sums stay below 2^32 in both halves: at most 768 / 1280 each).
+// One workgroup: the per-workgroup totals -> exclusive offsets (in place), grand totals -> counts.  One pass over blk: vertices in
+// the low and faces in the high half of one 64-bit word per workgroup.  No running sum leaves its half: vertices <= 3 n < 2^31 and
+// faces <= 5 n < 2^32 (3 n < 2^31 is the C ABI's limit on the volume).
 __global__ __launch_bounds__(kScanWG) void mesh_scan(const MeshArgs a) {
     __shared__ unsigned long long wsum[kScanWG / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long carry_v = 0, carry_f = 0;
-    for (int base = 0; base < a.nblk; base += kScanWG) {
-        const int b = base + threadIdx.x;
-        unsigned long long x = 0;
-        if (b < a.nblk) x = (unsigned long long)a.blk[2 * b] | (unsigned long long)a.blk[2 * b + 1] << 32;
-        unsigned long long s = x;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long y = __shfl_up(s, d, 64);
-            if (lane >= d) s += y;
-        }
-        if (lane == 63) wsum[wave] = s;
-        __syncthreads();
-        unsigned long long before = 0, sum = 0;
-#pragma unroll
-        for (int w = 0; w < kScanWG / 64; ++w) {
-            const unsigned long long t = wsum[w];
-            before += w < wave ? t : 0;
-            sum += t;
-        }
-        __syncthreads();      // wsum is rewritten by the next chunk
-        const unsigned long long ex = before + s - x;
-        if (b < a.nblk) {
-            a.blk[2 * b] = carry_v + (long long)(ex & 0xffffffffull);
-            a.blk[2 * b + 1] = carry_f + (long long)(ex >> 32);
-        }
-        carry_v += (long long)(sum & 0xffffffffull);
-        carry_f += (long long)(sum >> 32);
-    }
+    const unsigned long long sum = vscan::wg_scan_totals<kScanWG>(
+        a.nblk, wsum, [&](long long b) { return (unsigned long long)a.blk[2 * b] | (unsigned long long)a.blk[2 * b + 1] << 32; },
+        [&](long long b, unsigned long long ex) {
+            a.blk[2 * b] = (long long)(ex & 0xffffffffull);
+            a.blk[2 * b + 1] = (long long)(ex >> 32);
+        });
     if (threadIdx.x == 0) {
-        a.counts[0] = carry_v;
-        a.counts[1] = carry_f;
+        a.counts[0] = (long long)(sum & 0xffffffffull);
+        a.counts[1] = (long long)(sum >> 32);
     }
 }
 
@@ -451,7 +408,7 @@ __global__ __launch_bounds__(kMeshWG) void mesh_emit_vertices(const MeshArgs a) 
     const int p = blockIdx.x * kMeshWG + threadIdx.x;
     const unsigned m = p < a.n ? a.emask[p] : 0u;
     int total;
-    const int local = wg_exclusive_scan(__popc(m), lds4, &total);
+    const int local = vscan::wg_exclusive_scan<kMeshWG>((int)__popc(m), lds4, total);
     if (m == 0) return;
     const long long v0id = a.blk[2 * blockIdx.x] + local;
     a.firstv[p] = (int)v0id;
@@ -513,7 +470,7 @@ __global__ __launch_bounds__(kMeshWG) void mesh_emit_faces(const MeshArgs a) {
         }
     }
     int total;
-    const int local = wg_exclusive_scan(nt, lds4, &total);
+    const int local = vscan::wg_exclusive_scan<kMeshWG>(nt, lds4, total);
     if (nt == 0) return;
     const long long f0 = a.blk[2 * blockIdx.x + 1] + local;
     const int si = a.ny * a.nz, sj = a.nz;

@@ -23,7 +23,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _devmem, _lib
 from .meshing import BoundingBox, Mesh, load_mesh
 
 __all__ = ["accuracy", "completion", "completion_ratio", "chamfer", "nn_distance", "sample_surface", "crop_to_box",
@@ -41,15 +41,6 @@ def _points(x, device):
     t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
     t = t.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
     return t
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _aligned(nbytes, device):
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
 def _offsets(sizes, device):
@@ -77,12 +68,10 @@ def nn_distance(queries, refs, query_sizes=None, ref_sizes=None, return_index=Fa
     ro_h, ro_d = _offsets(rs, dev)
     dist = torch.empty(len(q), dtype=torch.float32, device=dev)
     index = torch.empty(len(q), dtype=torch.int32, device=dev) if return_index else None
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.vmapstep_nn_workspace_bytes(len(q), len(qs), ctypes.byref(nb)), lib)
-    ws, ws_ptr = _aligned(nb.value, dev)
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_nn_workspace_bytes, dev, len(q), len(qs))
     _lib.check(lib.vmapstep_nn_distance(q.data_ptr(), len(q), qo_d.data_ptr(), _i64p(qo_h), r.data_ptr(), len(r), ro_d.data_ptr(),
                                         _i64p(ro_h), len(qs), dist.data_ptr(), None if index is None else index.data_ptr(), ws_ptr,
-                                        nb.value, _stream(dev)), lib)
+                                        nbytes, _devmem.stream(dev)), lib)
     del ws
     return (dist, index) if return_index else dist
 
@@ -145,14 +134,12 @@ def _sample_sets(meshes, counts, seed=0, stream_id=0, set_base=0, randoms=None, 
         if u0.numel() != n or rr.numel() != 2 * n:
             raise _lib.VmapStepError("sample randoms: u0 [N] and r [N, 2]")
         rnd = _lib.SurfaceRandoms(u0.data_ptr(), rr.data_ptr())
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.vmapstep_surface_sample_workspace_bytes(len(f), ctypes.byref(nb)), lib)
-    ws, ws_ptr = _aligned(nb.value, dev)
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_surface_sample_workspace_bytes, dev, len(f))
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     _lib.check(lib.vmapstep_surface_sample(v.data_ptr(), len(v), f.data_ptr(), len(f), fo_d.data_ptr(), _i64p(fo_h), oo_d.data_ptr(),
                                            _i64p(oo_h), len(fs), seed, int(stream_id), int(set_base),
                                            None if rnd is None else ctypes.byref(rnd), pts.data_ptr(),
-                                           None if fidx is None else fidx.data_ptr(), ws_ptr, nb.value, _stream(dev)), lib)
+                                           None if fidx is None else fidx.data_ptr(), ws_ptr, nbytes, _devmem.stream(dev)), lib)
     del ws
     if return_face_index:
         return pts, fidx - torch.as_tensor(np.repeat(fo_h[:-1], counts), device=dev, dtype=torch.int32)
@@ -181,17 +168,15 @@ def crop_to_box(mesh, box):
     dev = _device()
     v, f = _mesh_arrays(mesh, dev)
     b = _box15(box)
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.vmapstep_clip_box_workspace_bytes(len(f), ctypes.byref(nb)), lib)
-    ws, ws_ptr = _aligned(nb.value, dev)
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_clip_box_workspace_bytes, dev, len(f))
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    stream = _stream(dev)
-    _lib.check(lib.vmapstep_clip_box_count(v.data_ptr(), len(v), f.data_ptr(), len(f), b, count.data_ptr(), ws_ptr, nb.value, stream), lib)
+    stream = _devmem.stream(dev)
+    _lib.check(lib.vmapstep_clip_box_count(v.data_ptr(), len(v), f.data_ptr(), len(f), b, count.data_ptr(), ws_ptr, nbytes, stream), lib)
     t = int(count.cpu())                    # the one host synchronisation
     if t == 0:
         return None
     tri = torch.empty(t, 3, 3, dtype=torch.float32, device=dev)
-    _lib.check(lib.vmapstep_clip_box_emit(v.data_ptr(), len(v), f.data_ptr(), len(f), b, tri.data_ptr(), t, ws_ptr, nb.value, stream), lib)
+    _lib.check(lib.vmapstep_clip_box_emit(v.data_ptr(), len(v), f.data_ptr(), len(f), b, tri.data_ptr(), t, ws_ptr, nbytes, stream), lib)
     del ws
     faces = torch.arange(3 * t, dtype=torch.int32, device=dev).reshape(t, 3)
     return Mesh(tri.reshape(-1, 3), faces, None)

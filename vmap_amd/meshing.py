@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _devmem, _lib
 
 
 class BoundingBox:
@@ -218,21 +218,13 @@ def _f12(affine):
     return (ctypes.c_float * 12)(*a.tolist())
 
 
-def _workspace(shape, device):
-    lib = _lib.load()
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.vmapstep_mesh_workspace_bytes(*shape, ctypes.byref(nb)), lib)
-    ws = torch.empty(nb.value + 256, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nb.value
-
-
 def grid_points(shape, affine, device="cuda:0"):
     """[nx*ny*nz, 3] float32 points A (i, j, k) + b in C order over the grid (one launch of vmapstep_mesh_grid_points)."""
     lib = _lib.load()
     nx, ny, nz = (int(s) for s in shape)
     dev = torch.device(device)
     pts = torch.empty(nx * ny * nz, 3, dtype=torch.float32, device=dev)
-    _lib.check(lib.vmapstep_mesh_grid_points(nx, ny, nz, _f12(affine), pts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), lib)
+    _lib.check(lib.vmapstep_mesh_grid_points(nx, ny, nz, _f12(affine), pts.data_ptr(), _devmem.stream(dev)), lib)
     return pts
 
 
@@ -246,8 +238,8 @@ def extract_mesh(volume: torch.Tensor, level: float = 0.5, affine=None):
     vol = volume.contiguous()
     dev = vol.device
     shape = tuple(int(s) for s in vol.shape)
-    ws, ws_ptr, nbytes = _workspace(shape, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_mesh_workspace_bytes, dev, *shape)
+    stream = _devmem.stream(dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     _lib.check(lib.vmapstep_mesh_count(vol.data_ptr(), *shape, float(level), counts.data_ptr(), ws_ptr, nbytes, stream), lib)
     nv, nf = (int(x) for x in counts.cpu())              # the one host synchronisation
