@@ -25,6 +25,7 @@ extern "C" void vmsim_set_sample_split(int nsplit) { g_sample_split = nsplit; } 
 // ABI v7 ray hand-off: when set, the next vmsim_step ignores `pcs` and hands the kernels origin / direction [n][R][3] + centres [n][3]
 static const float* g_ray_o = nullptr; static const float* g_ray_d = nullptr; static const float* g_ray_c = nullptr;
 extern "C" void vmsim_set_rays(const float* o, const float* d, const float* c) { g_ray_o = o; g_ray_d = d; g_ray_c = c; }
+extern "C" void vmsim_set_schedule(int s) { sim::set_schedule(s); }   // 0 round-robin (default), 1 / 2 wave-greedy forward / reverse (sim_runtime.h)
 static int g_split = 0;
 extern "C" void vmsim_set_split(int on) { g_split = on; }   // hidden 32: 1 = step_main_s32 (split-bf16 matrix pipe) instead of step_main_h32; 2 = ... with the six-product backward   
 

@@ -15,6 +15,10 @@ Idx3 g_gridDim{1, 1, 1}, g_blockDim{1, 1, 1};
 thread_local long g_yields = 0;
 
 static const std::function<void()>* g_body = nullptr;
+static int g_schedule = 0;
+static unsigned g_gx = 1, g_gy = 1;
+
+void set_schedule(int s) { g_schedule = s; }
 
 static void trampoline() {
     (*g_body)();
@@ -32,7 +36,7 @@ static void run_blocks(unsigned first, unsigned stride, unsigned grid, unsigned 
     blk.lds.resize(lds_bytes + 64);
     std::vector<char> stacks((size_t)block * kStack);
     for (unsigned b = first; b < grid; b += stride) {
-        g_blockIdx = {b, 0, 0};
+        g_blockIdx = {b % g_gx, (b / g_gx) % g_gy, b / (g_gx * g_gy)};
         std::memset(blk.lds.data(), 0xFF, blk.lds.size());   // 0xFFFFFFFF = NaN: poison
         blk.block_bar = Barrier{(int)block, 0, 0};
         int nw = (int)((block + kWave - 1) / kWave);
@@ -46,6 +50,8 @@ static void run_blocks(unsigned first, unsigned stride, unsigned grid, unsigned 
             Fiber& f = blk.fibers[t];
             f.done = false;
             f.tid = t;
+            f.shfl_turn = 0;
+            f.at_block_bar = false;
             f.stack = stacks.data() + (size_t)t * kStack;
             getcontext(&f.ctx);
             f.ctx.uc_stack.ss_sp = f.stack;
@@ -55,13 +61,37 @@ static void run_blocks(unsigned first, unsigned stride, unsigned grid, unsigned 
         }
         unsigned remaining = block;
         long guard = 0;
+        const int sched = g_schedule;
         while (remaining) {
-            for (unsigned t = 0; t < block; ++t) {
-                Fiber& f = blk.fibers[t];
-                if (f.done) continue;
-                g_cur = &f;
-                swapcontext(&g_sched, &f.ctx);
-                if (f.done) --remaining;
+            if (sched == 0) {
+                for (unsigned t = 0; t < block; ++t) {
+                    Fiber& f = blk.fibers[t];
+                    if (f.done) continue;
+                    g_cur = &f;
+                    swapcontext(&g_sched, &f.ctx);
+                    if (f.done) --remaining;
+                }
+            } else {
+                // wave-greedy: sweep one wave's fibers until none of them can run (done, or at the workgroup barrier in a
+                // generation that has not ended), then the next wave
+                for (int i = 0; i < nw; ++i) {
+                    const int w = sched == 1 ? i : nw - 1 - i;
+                    const unsigned t0 = (unsigned)w * kWave, t1 = std::min(block, t0 + kWave);
+                    bool ran = true;
+                    long sweeps = 0;
+                    while (ran) {
+                        ran = false;
+                        for (unsigned t = t0; t < t1; ++t) {
+                            Fiber& f = blk.fibers[t];
+                            if (f.done || (f.at_block_bar && blk.block_bar.gen == f.block_gen)) continue;
+                            g_cur = &f;
+                            swapcontext(&g_sched, &f.ctx);
+                            if (f.done) --remaining;
+                            ran = true;
+                        }
+                        if (++sweeps > 50000000L) { std::fprintf(stderr, "sim: deadlock inside a wave (barrier mismatch?)\n"); std::abort(); }
+                    }
+                }
             }
             if (++guard > 50000000L) { std::fprintf(stderr, "sim: deadlock (barrier mismatch?)\n"); std::abort(); }
         }
@@ -70,8 +100,13 @@ static void run_blocks(unsigned first, unsigned stride, unsigned grid, unsigned 
     g_cur = nullptr;
 }
 
-void launch(unsigned grid, unsigned block, size_t lds_bytes, const std::function<void()>& body) {
-    g_gridDim = {grid, 1, 1};
+void launch(unsigned grid, unsigned block, size_t lds_bytes, const std::function<void()>& body) { launch3(grid, 1, 1, block, lds_bytes, body); }
+
+void launch3(unsigned gx, unsigned gy, unsigned gz, unsigned block, size_t lds_bytes, const std::function<void()>& body) {
+    const unsigned grid = gx * gy * gz;
+    g_gx = gx;
+    g_gy = gy;
+    g_gridDim = {gx, gy, gz};
     g_blockDim = {block, 1, 1};
     g_body = &body;
     unsigned nt = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));

@@ -12,6 +12,7 @@ import torch
 
 import eval_oracle as eo
 from conftest import ROOT, load_golden
+from geom_checks import check_clip_against_oracle, check_nn as _check_nn, rotation_qr, whole_triangle_case
 
 pytestmark = pytest.mark.gpu
 
@@ -21,21 +22,6 @@ TILE, QB = 512, 2048            # the kernel's ref tile and queries per work ite
 def _ev():
     from vmap_amd import evaluation
     return evaluation
-
-
-def _check_nn(q, r, d, i, check_index=True):
-    q64, r64 = np.asarray(q, np.float64), np.asarray(r, np.float64)
-    d64, i64 = eo.nn(q64, r64)
-    L = max(np.abs(q64).max(), np.abs(r64).max())
-    bound = 1e-6 * (d64 + L)
-    err = np.abs(d.astype(np.float64) - d64)
-    assert (err <= bound).all(), f"worst {err.max():.3g} vs bound {bound[err.argmax()]:.3g}"
-    if check_index:
-        sep = eo.runner_up_gap(q64, r64) > 2 * bound
-        np.testing.assert_array_equal(i[sep], i64[sep])
-        # the chosen ref is (within the bound) a nearest one wherever it differs
-        dd = np.linalg.norm(q64 - r64[i], axis=1)
-        assert (np.abs(dd - d64) <= 2 * bound).all()
 
 
 def _cloud(kind, n, rng, offset=0.0):
@@ -257,9 +243,7 @@ def test_sampling_philox_mode():
     assert torch.equal(both[1000:], ev._sample_sets([m], [n], seed=123, set_base=5))
 
 
-def _rotation(rng):
-    q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
-    return q * np.sign(np.linalg.det(q))
+_rotation = rotation_qr
 
 
 def test_clip_matches_the_float64_clipper():
@@ -273,26 +257,9 @@ def test_clip_matches_the_float64_clipper():
     f = np.arange(len(v), dtype=np.int32).reshape(-1, 3)[rng.permutation(6000)]
     m = Mesh(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), None)
     box = BoundingBox(center=[4.1, 3.9, 4.2], R=_rotation(rng), extent=[1.8, 1.2, 2.0])
-    box32 = [np.float32(box.center).astype(np.float64), box.R.astype(np.float32).astype(np.float64), box.extent.astype(np.float32).astype(np.float64)]
-    want = eo.clip_mesh(v, f, *box32)
     got = ev.crop_to_box(m, box)
-    tri = got.vertices.cpu().numpy().reshape(-1, 3, 3).astype(np.float64)
-    assert got.faces.shape[0] == len(tri) and len(tri) == len(want)
-    L = np.abs(want).max()
-    err = np.abs(tri - want).max(axis=(1, 2))
-    # a cut along an edge nearly parallel to its plane is ill-conditioned in float32: the bulk within 1e-5 L, all within 1e-3 L
-    assert np.quantile(err, 0.999) <= 1e-5 * L and err.max() <= 1e-3 * L
-    assert abs(eo.soup_area(tri) - eo.soup_area(want)) <= 1e-5 * eo.soup_area(want)
-    local = (tri.reshape(-1, 3) - box32[0]) @ box32[1]
-    assert (np.abs(local) <= box32[2] / 2 + 1e-5 * L).all()
-    # triangles inside the box: bit-unchanged
-    loc_v = (v.astype(np.float64) - box32[0]) @ box32[1]
-    inside = (np.abs(loc_v[f]) < box32[2] / 2 - 1e-3).all(axis=(1, 2))
-    assert inside.sum() > 100
-    counts = np.array([max(len(eo.clip_polygon(v[x].astype(np.float64), *box32)) - 2, 0) for x in f])
-    first = np.concatenate([[0], np.cumsum(counts)])[:-1]
-    got32 = got.vertices.cpu().numpy().reshape(-1, 3, 3)
-    np.testing.assert_array_equal(got32[first[inside]], v[f[inside]])
+    assert got.faces.shape[0] == got.vertices.shape[0] // 3
+    check_clip_against_oracle(v, f, got.vertices.cpu().numpy().reshape(-1, 3, 3), box.center, box.R, box.extent)
     # everything outside: None; and determinism
     assert ev.crop_to_box(m, BoundingBox(center=[40, 40, 40], R=np.eye(3), extent=[1, 1, 1])) is None
     assert torch.equal(ev.crop_to_box(m, box).vertices, got.vertices)
@@ -303,24 +270,9 @@ def test_clip_of_whole_triangles_across_scan_chunks(nblk):
     """``nblk`` blocks of 256 faces (the last one partial), so that clip_scan ends on, at and past its chunks of 1024 block totals.
     Every triangle lies wholly inside the box or wholly beyond one of its planes, so the crop is v[f[inside]] bit for bit, in face
     order.  Runs of whole blocks keep nothing: totals of zero inside the scan."""
-    rng = np.random.default_rng(nblk)
     ev = _ev()
     from vmap_amd.meshing import BoundingBox, Mesh
-    nf = 256 * nblk - 5
-    R = _rotation(rng)
-    centre, extent = np.array([4.1, 3.9, 4.2]), np.array([1.8, 1.2, 2.0])
-    inside = rng.random(nf) < 0.5
-    inside[256 * 3:256 * 7] = False
-    inside[256 * (nblk - 4):256 * (nblk - 2)] = False
-    inside[[0, nf - 1]] = True
-    # local centres: inside at least 0.1 from every plane, outside at least 0.1 beyond the +- plane of one axis; triangles of 0.02
-    loc = rng.uniform(-1, 1, (nf, 3)) * (extent / 2 - 0.1)
-    ax = rng.integers(0, 3, nf)
-    out = ~inside
-    loc[out, ax[out]] = (rng.choice([-1.0, 1.0], out.sum()) * (extent[ax[out]] / 2 + 0.1 + rng.uniform(0, 1, out.sum())))
-    v = ((loc @ R.T + centre)[:, None, :] + rng.uniform(-0.02, 0.02, (nf, 3, 3))).reshape(-1, 3).astype(np.float32)
-    f = np.arange(3 * nf, dtype=np.int32).reshape(-1, 3)
-    f = f[:, rng.permutation(3)]
+    v, f, inside, R, centre, extent = whole_triangle_case(nblk)
     got = ev.crop_to_box(Mesh(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda(), None), BoundingBox(center=centre, R=R, extent=extent))
     assert got.faces.shape[0] == inside.sum()
     np.testing.assert_array_equal(got.vertices.cpu().numpy().reshape(-1, 3, 3), v[f[inside]])

@@ -8,6 +8,7 @@ import torch
 
 import mesh_oracle as mo
 from conftest import load_golden
+from geom_checks import check_mesh_against_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -30,21 +31,9 @@ def _volumes():
 
 
 def _check_against_oracle(vol, mesh, affine=None):
-    v, f, n, _ = mo.marching_cubes(vol, 0.5, affine)
     gv, gf, gn, gc = mesh.numpy()
-    assert gc is None
-    np.testing.assert_array_equal(gf, f)
-    assert gv.shape == v.shape and np.abs(gv - v).max() < 1e-5 * (1 if affine is None else np.abs(v).max() + 1)
-    # normals: where the interpolated gradient is not (nearly) zero
-    g = mo.gradient(vol)
-    _, _, _, eid = mo.marching_cubes(vol, 0.5)
-    pt, ax = eid // 3, eid % 3
-    idx = np.stack(np.unravel_index(pt, vol.shape), -1)
-    idx1 = idx.copy()
-    idx1[np.arange(len(idx)), ax] += 1
-    ok = (np.linalg.norm(g[tuple(idx.T)], axis=1) > 1e-6) | (np.linalg.norm(g[tuple(idx1.T)], axis=1) > 1e-6)
-    ok &= np.linalg.norm(n, axis=1) > 0.5
-    assert np.abs(gn[ok] - n[ok]).max() < 1e-4
+    assert gc is None and gn is not None
+    check_mesh_against_oracle(vol, gv, gf, gn, affine)
 
 
 @pytest.mark.parametrize("name,vol", list(_volumes()), ids=lambda x: x if isinstance(x, str) else "")

@@ -56,24 +56,10 @@ int finalize_ws8(const vk::FinalizeArgs& f, const vk::FinalizeHot& h, const int*
 int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, long long n_points, hipStream_t st);
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st);   // a.obj_max != null: the split form (two launches)
 
-// The mesh, evaluation and bounds families below take their block sizes from launch_geometry.h, which their kernels include too.
-inline size_t ws_up(size_t x) { return (x + 255) / 256 * 256; }       // workspace sections start 256-byte aligned
-inline long long ceil_div(long long x, long long d) { return (x + d - 1) / d; }
-
+// The mesh, evaluation and bounds families below take their block sizes, workspace layouts and launch plans from launch_geometry.h
+// (vl::mesh_layout, nn_layout, nn_plan_host, surface_sample_bytes, clip_box_bytes, unproject_blocks, unproject_layout, obb_chunks).
 // k_mesh.hip: marching cubes (mesh_kernels.h) and the dense grid Trainer.meshing queries.  The workspace of a [nx][ny][nz] volume:
 // per-workgroup (vertices, faces) int64 pairs, then the first vertex id (int32) and the crossing-edge mask (uint8) of every point.
-struct MeshLayout {
-    long long n; int nblk; size_t off_firstv, off_emask, bytes;
-};
-inline MeshLayout mesh_layout(int nx, int ny, int nz) {
-    MeshLayout l;
-    l.n = (long long)nx * ny * nz;
-    l.nblk = (int)ceil_div(l.n, vm::kMeshWG);
-    l.off_firstv = ws_up((size_t)l.nblk * 2 * sizeof(long long));
-    l.off_emask = l.off_firstv + ws_up((size_t)l.n * sizeof(int));
-    l.bytes = l.off_emask + ws_up((size_t)l.n);
-    return l;
-}
 int mesh_grid_points(int nx, int ny, int nz, const float affine[12], float* points, hipStream_t st);
 int mesh_count(const float* volume, int nx, int ny, int nz, float level, long long* counts, void* workspace, hipStream_t st);
 // affine / ninv: null = index space; otherwise [A | b] rows and the inverse transpose of A (rows, for the normals)
@@ -82,50 +68,13 @@ int mesh_emit(const float* volume, int nx, int ny, int nz, float level, const fl
 
 // k_eval.hip: mesh evaluation (eval_kernels.h).  Nearest neighbours: the workspace holds the per-set prefix of the work items
 // (int64 [n_sets + 1]) and one packed (squared distance, index) key per query (uint64 [n_queries]).
-struct NnLayout {
-    size_t off_keys, bytes;
-};
-inline NnLayout nn_layout(long long n_queries, int n_sets) {
-    NnLayout l;
-    l.off_keys = ws_up((size_t)(n_sets + 1) * sizeof(long long));
-    l.bytes = l.off_keys + ws_up((size_t)n_queries * sizeof(unsigned long long));
-    return l;
-}
-// The launch plan from the host copies of the offsets: refs per work item (a multiple of the ref tile, ve::kNnTile) chosen so
-// that about kNnItemsTarget items exist (8 per CU), and the item count nn_plan computes on the device by the same formula.
-struct NnPlan {
-    long long n_queries, q_begin, q_end, rchunk, items;
-};
-constexpr long long kNnItemsTarget = 2048;
-inline NnPlan nn_plan_host(const long long* qo, const long long* ro, int n_sets, long long n_queries) {
-    constexpr long long qb = ve::kNnQB, tile = ve::kNnTile;
-    NnPlan p;
-    p.n_queries = n_queries; p.q_begin = qo[0]; p.q_end = qo[n_sets];
-    long long work = 0;                                   // sum over sets of (query blocks x refs)
-    for (int s = 0; s < n_sets; ++s) {
-        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
-        if (nq > 0) work += ceil_div(nq, qb) * nr;
-    }
-    long long rc = ceil_div(work, kNnItemsTarget);
-    rc = rc < 2 * tile ? 2 * tile : rc;
-    rc = ceil_div(rc, tile) * tile;
-    p.rchunk = rc;
-    p.items = 0;
-    for (int s = 0; s < n_sets; ++s) {
-        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
-        if (nq > 0 && nr > 0) p.items += ceil_div(nq, qb) * ceil_div(nr, rc);
-    }
-    return p;
-}
 int nn_distance(const NnPlan& p, const float* queries, const long long* qo, const float* refs, const long long* ro, int n_sets,
                 float* dist, int* index, void* workspace, hipStream_t st);
-// surface sampling: the workspace is the float64 cumulative area of every face
-inline size_t surface_sample_bytes(long long n_faces) { return ws_up((size_t)n_faces * sizeof(double)); }
+// surface sampling: the workspace (surface_sample_bytes) is the float64 cumulative area of every face
 int surface_sample(const float* vertices, long long n_vertices, const int* faces, const long long* fo, const long long* oo, int n_sets,
                    long long o_begin, long long o_end, unsigned long long seed, unsigned stream_id, int set_base, const double* u0,
                    const float* r, float* points, int* face_index, void* workspace, hipStream_t st);
-// box clipping: the workspace is one int64 per block of ve::kEvalWG faces (triangles per block, then their exclusive prefix)
-inline size_t clip_box_bytes(long long n_faces) { return ws_up((size_t)ceil_div(n_faces, ve::kEvalWG) * sizeof(long long)) + 256; }
+// box clipping: the workspace (clip_box_bytes) is one int64 per block of ve::kEvalWG faces
 int clip_box_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float box[15], long long* count,
                    void* workspace, hipStream_t st);
 int clip_box_emit(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float box[15], float* triangles,
@@ -138,31 +87,11 @@ struct UnprojectFrames {
     int n_slots, width, height;
     float fx, fy, cx, cy;
 };
-inline int unproject_blocks(int width, int height) { return (int)ceil_div((long long)width * height, vb::kPixBlock); }
-struct UnprojectLayout {
-    size_t off_enc, bytes;
-};
-inline UnprojectLayout unproject_layout(int n_pairs, int n_obj, int width, int height) {
-    UnprojectLayout l;
-    l.off_enc = ws_up((size_t)n_pairs * unproject_blocks(width, height) * sizeof(long long)) + 256;
-    l.bytes = l.off_enc + ws_up((size_t)n_obj * 6 * sizeof(unsigned));
-    return l;
-}
 int unproject_count(const UnprojectFrames& f, const int* pairs, const int* first_pair, int n_obj, int n_pairs, long long* offsets,
                     float* bounds, void* workspace, hipStream_t st);
 int unproject_emit(const UnprojectFrames& f, const int* pairs, const int* first_pair, int n_obj, int n_pairs, float* points,
                    long long n_points, void* workspace, hipStream_t st);
-// The automatic launch geometry of obb_extents: point chunks per object so that about kObbBlocksTarget workgroups exist (8 per CU),
-// never more than the largest object has tiles of vb::kObbTile points.  The result does not depend on it (minimum and maximum are exact).
-constexpr long long kObbBlocksTarget = 2048;
-inline int obb_chunks(const long long* po, int n_obj, int K) {
-    long long most = 0;
-    for (int o = 0; o < n_obj; ++o) most = po[o + 1] - po[o] > most ? po[o + 1] - po[o] : most;
-    const long long tiles = ceil_div(most, vb::kObbTile), per_chunk = ceil_div(K, vb::kObbBlock) * n_obj;
-    long long c = ceil_div(kObbBlocksTarget, per_chunk);
-    c = c > tiles ? tiles : c;
-    return (int)(c < 1 ? 1 : c > 65535 ? 65535 : c);
-}
+// chunks: point chunks per object (vl::obb_chunks picks it); the result does not depend on it (minimum and maximum are exact)
 int obb_extents(const float* points, const long long* po, int n_obj, const float* center, const float* rotations, long long set_stride,
                 int K, int chunks, float* lo, float* hi, hipStream_t st);
 int cloud_moments(const float* points, const long long* po, int n_obj, const float* center, double* moments, hipStream_t st);

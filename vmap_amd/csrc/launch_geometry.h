@@ -1,7 +1,9 @@
 // launch_geometry.h - the launch geometry of the mesh, evaluation and bounds families: the constants that both the kernels
 // (mesh_kernels.h, eval_kernels.h, bounds_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
-// constexpr values only, no device code: the C ABI unit sizes workspaces from them without compiling anyone's kernels.
+// constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
+// without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
+#include <cstddef>
 
 namespace vm {
 constexpr int kMeshWG = 256;               // points per workgroup of count / emit
@@ -26,3 +28,94 @@ constexpr int kObbCand = 4;                // candidates per lane
 constexpr int kObbBlock = kBoundsWG * kObbCand;   // candidates per block
 constexpr int kObbTile = 512;              // points per LDS tile (float4 each: 8 KiB)
 }  // namespace vb
+
+// ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
+namespace vl {
+
+inline size_t ws_up(size_t x) { return (x + 255) / 256 * 256; }       // workspace sections start 256-byte aligned
+inline long long ceil_div(long long x, long long d) { return (x + d - 1) / d; }
+
+// Marching cubes.  The workspace of a [nx][ny][nz] volume: per-workgroup (vertices, faces) int64 pairs, then the first vertex id
+// (int32) and the crossing-edge mask (uint8) of every point.
+struct MeshLayout {
+    long long n; int nblk; size_t off_firstv, off_emask, bytes;
+};
+inline MeshLayout mesh_layout(int nx, int ny, int nz) {
+    MeshLayout l;
+    l.n = (long long)nx * ny * nz;
+    l.nblk = (int)ceil_div(l.n, vm::kMeshWG);
+    l.off_firstv = ws_up((size_t)l.nblk * 2 * sizeof(long long));
+    l.off_emask = l.off_firstv + ws_up((size_t)l.n * sizeof(int));
+    l.bytes = l.off_emask + ws_up((size_t)l.n);
+    return l;
+}
+
+// Nearest neighbours: the workspace holds the per-set prefix of the work items (int64 [n_sets + 1]) and one packed (squared
+// distance, index) key per query (uint64 [n_queries]).
+struct NnLayout {
+    size_t off_keys, bytes;
+};
+inline NnLayout nn_layout(long long n_queries, int n_sets) {
+    NnLayout l;
+    l.off_keys = ws_up((size_t)(n_sets + 1) * sizeof(long long));
+    l.bytes = l.off_keys + ws_up((size_t)n_queries * sizeof(unsigned long long));
+    return l;
+}
+// The launch plan from the host copies of the offsets: refs per work item (a multiple of the ref tile, ve::kNnTile) chosen so
+// that about kNnItemsTarget items exist (8 per CU), and the item count nn_plan computes on the device by the same formula.
+struct NnPlan {
+    long long n_queries, q_begin, q_end, rchunk, items;
+};
+constexpr long long kNnItemsTarget = 2048;
+inline NnPlan nn_plan_host(const long long* qo, const long long* ro, int n_sets, long long n_queries) {
+    constexpr long long qb = ve::kNnQB, tile = ve::kNnTile;
+    NnPlan p;
+    p.n_queries = n_queries; p.q_begin = qo[0]; p.q_end = qo[n_sets];
+    long long work = 0;                                   // sum over sets of (query blocks x refs)
+    for (int s = 0; s < n_sets; ++s) {
+        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
+        if (nq > 0) work += ceil_div(nq, qb) * nr;
+    }
+    long long rc = ceil_div(work, kNnItemsTarget);
+    rc = rc < 2 * tile ? 2 * tile : rc;
+    rc = ceil_div(rc, tile) * tile;
+    p.rchunk = rc;
+    p.items = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        const long long nq = qo[s + 1] - qo[s], nr = ro[s + 1] - ro[s];
+        if (nq > 0 && nr > 0) p.items += ceil_div(nq, qb) * ceil_div(nr, rc);
+    }
+    return p;
+}
+
+// surface sampling: the workspace is the float64 cumulative area of every face
+inline size_t surface_sample_bytes(long long n_faces) { return ws_up((size_t)n_faces * sizeof(double)); }
+// box clipping: the workspace is one int64 per block of ve::kEvalWG faces (triangles per block, then their exclusive prefix)
+inline size_t clip_box_bytes(long long n_faces) { return ws_up((size_t)ceil_div(n_faces, ve::kEvalWG) * sizeof(long long)) + 256; }
+
+// Unprojection: the workspace holds one int64 per (pair, vb::kPixBlock pixels) and the encoded coordinate extremes of every object
+// (uint32 [n_obj][6]).
+inline int unproject_blocks(int width, int height) { return (int)ceil_div((long long)width * height, vb::kPixBlock); }
+struct UnprojectLayout {
+    size_t off_enc, bytes;
+};
+inline UnprojectLayout unproject_layout(int n_pairs, int n_obj, int width, int height) {
+    UnprojectLayout l;
+    l.off_enc = ws_up((size_t)n_pairs * unproject_blocks(width, height) * sizeof(long long)) + 256;
+    l.bytes = l.off_enc + ws_up((size_t)n_obj * 6 * sizeof(unsigned));
+    return l;
+}
+
+// The automatic launch geometry of obb_extents: point chunks per object so that about kObbBlocksTarget workgroups exist (8 per CU),
+// never more than the largest object has tiles of vb::kObbTile points.  The result does not depend on it (minimum and maximum are exact).
+constexpr long long kObbBlocksTarget = 2048;
+inline int obb_chunks(const long long* po, int n_obj, int K) {
+    long long most = 0;
+    for (int o = 0; o < n_obj; ++o) most = po[o + 1] - po[o] > most ? po[o + 1] - po[o] : most;
+    const long long tiles = ceil_div(most, vb::kObbTile), per_chunk = ceil_div(K, vb::kObbBlock) * n_obj;
+    long long c = ceil_div(kObbBlocksTarget, per_chunk);
+    c = c > tiles ? tiles : c;
+    return (int)(c < 1 ? 1 : c > 65535 ? 65535 : c);
+}
+
+}  // namespace vl
