@@ -72,6 +72,8 @@ typedef struct vmapstep_tuning {
                                    /* row group, never its one-thread-per-quad form (A/B: same bits either way)    */
     int32_t ws_flags;              /* step_main_ws, measurement: bit 0 = never use single-tile rounds, bit 1 =     */
                                    /* always three-tile rounds (hidden 128), bit 2 = never three-tile rounds (A/B) */
+                                   /* step_main_s32 (hidden 32), measurement build only: bit 3 = the B_layer.weight   */
+                                   /* gradient summed with one butterfly per value (A/B: same bits either way)        */
 } vmapstep_tuning;
 
 typedef struct vmapstep_shape {

@@ -34,6 +34,7 @@
 #define VS_ABL 0
 #endif
 #include "step_kernels.h"
+#include "wave_reduce.h"
 
 // Measurement builds only (tests/tools/build_variant.py ... -DVS_ABL=<mask>; results WRONG on purpose - the product never defines it):
 // bit 7: step_finalize_s32 does not rewrite the parameter image; bit 4: only the partial-gradient global stores are skipped; bit 5: the finishing (staged reads, sums, stores) is skipped, the staging writes stay;
@@ -803,7 +804,8 @@ __device__ __forceinline__ void stage_get_s(float (&q)[4], const float* stage, i
 // ---------------------------------------------------------------------------------------------------------
 // step_main_s32<BWD, MULTI, STAMPS, W3>:  W3 = float32 weights as three planes (false: bf16 weights, one plane)
 // ---------------------------------------------------------------------------------------------------------
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false>
+// PV (measurement build only): the B_layer.weight gradient with one butterfly per value, the form before wave_reduce.h
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false>
 __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     static_assert(!B6 || (W3 && BWD), "six-product backward: float32 weights, training instantiations");
     using I = Img32s;
@@ -1230,14 +1232,24 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         stage_put_s(stg1, acc, wave, p31, hi);                      // block 11
         fin_chunk<1, H + kEmb1, MULTI>(1, fs, qacc[8], stg0, out + F::W_CAT + H, out + F::B_CAT, 2, kEmb1, wave, p31, hi);
         float keep[3] = {0.0f, 0.0f, 0.0f};                         // value v = 3 i + j lives on lane (lane & 15) == (v & 15) of the half's second row, slot v >> 4
+        if constexpr (PV) {                                         // tuning.ws_flags bit 3: the source before wave_reduce.h, word for word, in an instantiation of
+            // its own (as a run-time branch beside the new form it was compiled differently: products packed in pairs, other bits)
 #pragma unroll
-        for (int i = 0; i < 11; ++i) {
+            for (int i = 0; i < 11; ++i) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int v = 3 * i + j;
-                const float sum = wv::half_sum32_hi_row(dproj[i] * t[j]);      // this lane's direction: hi ? 11 + i : i (the eleventh of the hi = 1 half is a dummy: dproj = 0)
-                keep[v >> 4] = (lane & 15) == (v & 15) ? sum : keep[v >> 4];
+                for (int j = 0; j < 3; ++j) {
+                    const int v = 3 * i + j;
+                    const float sum = wv::half_sum32_hi_row(dproj[i] * t[j]);
+                    keep[v >> 4] = (lane & 15) == (v & 15) ? sum : keep[v >> 4];
+                }
             }
+        } else {
+            // this lane's direction: hi ? 11 + i : i (the eleventh of the hi = 1 half is a dummy: dproj = 0).  Values 0..31 as two
+            // transposing butterflies (wave_reduce.h: the sum tree of half_sum32_hi_row, lane c left with value 16 sl + c), value 32 alone
+#pragma unroll
+            for (int sl = 0; sl < 2; ++sl)
+                keep[sl] = wv::half_dots32_scatter16([&](int c, float& d, float& tt) { const int v = 16 * sl + c; d = dproj[v / 3]; tt = t[v % 3]; }, lane);
+            keep[2] = wv::half_dot32_hi_row(dproj[10], t[2], lane);
         }
         if (lane & 16) {
 #pragma unroll
@@ -1305,9 +1317,9 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 #undef VS_MARK
 }
 
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false>
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false>
 __global__ __launch_bounds__(kWG, 1) void step_main_s32(const StepArgs a) {
-    step_main_s32_body<BWD, MULTI, STAMPS, W3, B6>(a);
+    step_main_s32_body<BWD, MULTI, STAMPS, W3, B6, PV>(a);
 }
 
 }  // namespace vk

@@ -92,6 +92,8 @@ struct StepArgs {
     // the workgroups' rows of partial gradients: PR floats each (= PP: the parameters' flat order; step_main_ws / _wp: RowWs<NB>::PR,
     // block-native order, with row_tab [PR] = the flat parameter behind every row element or -1, written by step_prep_ws)
     int PR; int* row_tab;
+    int ab_flags;                      // measurement build (-DVMAPSTEP_AB) only, hidden 32: bit 0 = the launcher takes the step_main_s32 instantiation that reduces the
+                                       // B_layer.weight gradient with one butterfly per value (tuning.ws_flags bit 3; float32 weights, training); no kernel reads it
 };
 
 // Sample point `smp` of ray `ray` of object `obj` in the object frame: read from the points tensor (train.py:272 batch_input_pcs),

@@ -170,6 +170,10 @@ int make_plan(const vmapstep_shape* sh, int max_steps, Plan& pl, const Layout& L
     // every further round re-reads and re-writes its 1.4 MB gradient row and the step becomes bound by that traffic - still ahead
     // of the exact-fp32 kernels (the reference's own iMAP batch, 4800 rays: 3.50 -> 2.38 ms, profiles/r04i_*)
     if (pl.generic && sh->hidden == 256 && sh->samples <= 32 && (force == VMAPSTEP_KERNEL_AUTO || force == VMAPSTEP_KERNEL_WS1)) pl.wide = 3;
+#ifndef VMAPSTEP_AB
+    if (pl.split && (tun.ws_flags & 8))      // hidden 32: the B_layer.weight gradient with one butterfly per value (A/B form of step_main_s32)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "this kernel form ships in the measurement build only (tests/tools/libvmapstep_ab.so: phase stamps and A/B forms no automatic plan launches)");
+#endif
     if ((force == VMAPSTEP_KERNEL_WS1 || force == VMAPSTEP_KERNEL_WP) && pl.wide < 3)
         return fail(VMAPSTEP_ERR_UNSUPPORTED, "VMAPSTEP_KERNEL_WS1 / _WP: hidden 64 / 128 with at most 64 samples per ray (_WS1 also hidden 256 with at most 32)");
     pl.G = (pl.wide >= 3 ? vk::ImgWs<4>::kPts : pl.wide == 1 ? vk::kWideTile : vk::kMaxPts) / sh->samples;
@@ -298,6 +302,7 @@ void fill_step_args(vk::StepArgs& a, const vmapstep_shape* sh, const Plan& pl, c
     a.wide = pl.wide;
     a.split = pl.split ? 1 : 0;
     a.bwd6 = pl.bwd6 ? 1 : 0;
+    a.ab_flags = (pl.split && (tuning_of(sh).ws_flags & 8)) ? 1 : 0;
     a.stats = reinterpret_cast<float*>(ws + pl.off_stats);
     a.flags = reinterpret_cast<int*>(ws + pl.off_flags);
     a.part_loss = reinterpret_cast<float*>(ws + pl.off_ploss);
