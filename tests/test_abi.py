@@ -222,3 +222,31 @@ def test_product_library_carries_the_planned_forms_only():
     for sh, tun in [(_lib.Shape(20, 120, 10, 32, 0), dict(kernel=_lib.KERNEL_H32_F32)), (_lib.Shape(1, 1200, 14, 128, 0), dict(kernel=_lib.KERNEL_GEN)),
                     (_lib.Shape(1, 1200, 14, 128, 0), dict(ws_flags=4)), (_lib.Shape(1, 150, 14, 128, 0), dict(ws_flags=1))]:
         assert plan(prod, sh, **tun)[0] == 0, tun
+
+
+SAMPLER_LIMITS = [  # (what, at the limit, one past it): width, height, frames, samples_per_frame, n_bins_cam2surface, n_bins
+    ("S <= 32", (64, 48, 10, 6, 16, 16), (64, 48, 10, 6, 17, 16)),
+    ("n_bins <= 16", (64, 48, 10, 6, 1, 16), (64, 48, 10, 6, 1, 17)),
+    ("W <= 4095", (4095, 48, 10, 6, 1, 9), (4096, 48, 10, 6, 1, 9)),
+    ("H <= 4095", (64, 4095, 10, 6, 1, 9), (64, 4096, 10, 6, 1, 9)),
+    ("F * P <= 2^24", (64, 48, 4096, 4096, 1, 9), (64, 48, 4097, 4096, 1, 9)),
+]
+
+
+@pytest.mark.parametrize("what,at,past", SAMPLER_LIMITS, ids=[c[0] for c in SAMPLER_LIMITS])
+@pytest.mark.parametrize("entry", ["vmapstep_sample_frame", "vmapstep_sample_frame_rays"])
+def test_sampler_refuses_shapes_past_its_limits(entry, what, at, past):
+    """sample_frame_impl's limits (the kernel's register arrays, the 12-bit pixel code, the staging index): a shape one past a limit
+    is VMAPSTEP_ERR_UNSUPPORTED; the shape AT the limit passes that check and gets as far as the next one - the workspace, given
+    here with zero bytes (VMAPSTEP_ERR_WORKSPACE).  Both answers come before anything touches a device; no pointer is read."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 4
+    n_out = 6 if entry == "vmapstep_sample_frame" else 9           # pcs, z ... depth_mask / ray_o, ray_d, center, pcs, z ... depth_mask
+
+    def call(shape):
+        cfg = _lib.SampleCfg(*shape, 60.0, 55.0, 31.5, 23.5, 0.0, 0.1, 0.05)
+        return getattr(lib, entry)(ctypes.byref(cfg), p, 2, *([p] * n_out), 7, 0, None, p, 0, None)
+
+    assert call(at) == -3 and b"sampler workspace" in lib.vmapstep_last_error(), what                   # VMAPSTEP_ERR_WORKSPACE
+    assert call(past) == -2 and b"sampler limits" in lib.vmapstep_last_error(), what                    # VMAPSTEP_ERR_UNSUPPORTED

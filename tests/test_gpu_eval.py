@@ -243,6 +243,26 @@ def test_sampling_philox_mode():
     assert torch.equal(both[1000:], ev._sample_sets([m], [n], seed=123, set_base=5))
 
 
+def test_sampling_philox_mode_is_predicted_by_the_replica():
+    """_sample_sets drawing its own numbers, at the sizes of the executor's test (sets of 60 and 1500 faces, 300 and 900 points, a
+    64-bit seed, stream and set_base not zero): the faces eval_oracle.sample picks from philox_ref.surface_randoms, exactly, and its
+    points."""
+    from philox_ref import surface_randoms
+    rng = np.random.default_rng(6)
+    ev = _ev()
+    sets = [_random_mesh(rng, nv=40, nf=60, offset=2.0), _random_mesh(rng, nv=40, nf=1500, offset=2.0)]
+    counts = [300, 900]
+    seed, stream, set_base = 0x1234_5678_9ABC_DEF0, 3, 4
+    pts, fidx = ev._sample_sets([m for m, _, _ in sets], counts, seed=seed, stream_id=stream, set_base=set_base, return_face_index=True)
+    pts, fidx = pts.cpu().numpy(), fidx.cpu().numpy()
+    oo = np.concatenate([[0], np.cumsum(counts)])
+    for s, (_, v, f) in enumerate(sets):
+        u0, r = surface_randoms(counts[s], set_base + s, stream, seed)
+        p, fc = eo.sample(v, f, u0, r)
+        np.testing.assert_array_equal(fidx[oo[s]:oo[s + 1]], fc)
+        assert np.abs(pts[oo[s]:oo[s + 1]] - p).max() <= 1e-6 * np.abs(p).max()
+
+
 _rotation = rotation_qr
 
 

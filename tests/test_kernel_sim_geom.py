@@ -15,6 +15,7 @@ import mesh_oracle as mo
 import simlib
 from conftest import load_golden
 from geom_checks import check_clip_against_oracle, check_mesh_against_oracle, check_nn, nn_exempt_share, rotation_qr, whole_triangle_case
+from philox_ref import M32, philox4x32_10, surface_randoms
 
 SCHEDULES = (0, 1, 2)
 
@@ -300,23 +301,6 @@ def test_sim_nn_writes_only_its_query_range():
 
 # ---- surface sampling --------------------------------------------------------------------------------------------------------------
 
-M32 = 0xFFFFFFFF
-
-
-def philox4x32_10(counter, key):
-    """Philox4x32-10 in plain integers (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds of
-    (c0, c1, c2, c3) -> (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), the key bumped by the Weyl constants
-    after each.  No known-answer vector is pinned.  The multipliers and Weyl constants are the published ones, which the kernel uses
-    too: this function is independent of the kernel's in its structure (plain integers, one tuple per round), not in its constants."""
-    c0, c1, c2, c3 = counter
-    k0, k1 = key
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & M32, p1 & M32, ((p0 >> 32) ^ c3 ^ k1) & M32, p0 & M32
-        k0, k1 = (k0 + 0x9E3779B9) & M32, (k1 + 0xBB67AE85) & M32
-    return c0, c1, c2, c3
-
-
 def _surface_sets(rng, nfs, nv=300):
     """One vertex array, the sets' faces one after the other; zero-area faces and vertex indices outside [0, V) sprinkled in (never
     on a set's first or last face).  -> (v, f, fo, v_oracle, f_oracle): the oracle mesh reads an outside index as an appended origin."""
@@ -383,6 +367,8 @@ def test_sim_surface_cdf_and_test_mode_sampling():
 
 
 def test_sim_surface_philox_mode_is_predicted_by_plain_python():
+    """surface_sample drawing its own numbers against eval_oracle.sample fed with philox_ref.surface_randoms, whose Philox is held to
+    the published known-answer vectors by tests/test_philox.py."""
     rng = np.random.default_rng(6)
     v, f, fo, v_or, f_or = _surface_sets(rng, [60, 1500], nv=40)
     counts = [300, 900]
@@ -390,11 +376,11 @@ def test_sim_surface_philox_mode_is_predicted_by_plain_python():
     seed, stream, set_base = 0x1234_5678_9ABC_DEF0, 3, 4
     o = run3(lambda: simlib.sim_surface_sample(v, f, fo, oo, seed=seed, stream_id=stream, set_base=set_base))
     for s, n in enumerate(counts):
-        u0, r = np.empty(n), np.empty((n, 2), np.float32)
-        for j in range(n):
+        u0, r = surface_randoms(n, set_base + s, stream, seed)
+        for j in (0, 1, n - 1):                                          # the vectorised draw, spelled out in plain integers
             w = philox4x32_10((j, set_base + s, stream, 0), (seed & M32, seed >> 32))
-            u0[j] = float((w[0] << 21) | (w[1] >> 11)) * 2.0 ** -53
-            r[j] = np.float32(w[2] >> 8) * np.float32(2.0 ** -24), np.float32(w[3] >> 8) * np.float32(2.0 ** -24)
+            assert u0[j] == float((w[0] << 21) | (w[1] >> 11)) * 2.0 ** -53
+            assert tuple(r[j]) == (np.float32(w[2] >> 8) * np.float32(2.0 ** -24), np.float32(w[3] >> 8) * np.float32(2.0 ** -24))
         assert 0 <= u0.min() and u0.max() < 1 and 0.3 < u0.mean() < 0.7 and 0.3 < r.mean() < 0.7
         p, fc = eo.sample(v_or, f_or[fo[s]:fo[s + 1]], u0, r)
         np.testing.assert_array_equal(o["face_index"][oo[s]:oo[s + 1]], fc + fo[s])

@@ -1,30 +1,16 @@
 """Depth-guided sampler: oracle pinned to the real reference sampler, HIP kernel source on the
-simulator and (gpu tier) the device kernel against the oracle; statistical checks of the Philox mode."""
+simulator and (gpu tier) the device kernel against the oracle; statistical checks of the Philox mode and (gpu tier) its exact
+replay from tests/philox_ref.py (the executor's replay is tests/test_philox.py)."""
 import os
 
 import numpy as np
 import pytest
 
 import sampler_cases
+import sampler_checks
 import simlib
 from conftest import GOLDEN_DIR
-from oracle import sampler_oracle as so
-
-EPS, STOP = 0.1, 0.05
-
-
-def _oracle(sc, rnd):
-    return so.sample_object(sc["rgbs"], sc["depth"], sc["t_wc"], sc["bbox"], rnd["kf_ids"], rnd["u_w"], rnd["u_h"], rnd["u_z"],
-                            rnd["g_z"], sc["intr"], sc["center"], sc["n1"], sc["n2"], min_bound=sc["min_bound"], eps=EPS, stop_eps=STOP)
-
-
-def _check_against_oracle(out, k, o):
-    assert np.array_equal(out["sem"][k], o["labels"])
-    assert np.array_equal(out["depth_mask"][k].astype(bool), o["valid"])
-    assert np.array_equal(out["gt_depth"][k], o["depth"])
-    assert np.abs(out["gt_rgb"][k] - o["rgb"].astype(np.float32) / np.float32(255.0)).max() < 1e-7
-    assert np.abs(out["z"][k].astype(np.float64) - o["z"]).max() < 3e-6
-    assert np.abs(out["pcs"][k].astype(np.float64) - o["pcs"]).max() < 6e-6
+from sampler_checks import EPS, STOP, check_against_oracle as _check_against_oracle, oracle as _oracle
 
 
 @pytest.mark.parametrize("name", list(sampler_cases.CASES))
@@ -221,7 +207,7 @@ def test_sim_sampler_background_frame_size_equals_oracle():
 @pytest.mark.gpu
 def test_gpu_sampler_background_frame_size():
     """vmapstep_sample_frame at F * P = 24000 (refused with VMAPSTEP_ERR_UNSUPPORTED before): test mode == oracle; Philox
-    mode reproducible; the frame trains the background-shaped field (hidden 128, 1200 rays x 19 samples per step)."""
+    mode reproducible and equal to its replay (philox_ref.frame_randoms + the oracle); the frame trains the background-shaped field (hidden 128, 1200 rays x 19 samples per step)."""
     import torch
     from vmap_amd import sampler, step, synth
     dev = "cuda:0"
@@ -243,6 +229,8 @@ def test_gpu_sampler_background_frame_size():
     b = smp.sample()
     for k in a:
         assert torch.equal(a[k], b[k])
+    # ... and equal to its replay: 24000 rays run the unstaged form, where phase A - the keyframe and pixel draws - is evaluated twice
+    sampler_checks.check_replay({k: v.cpu().numpy() for k, v in a.items()}, [sc], 5, 1)
     S = sc["n1"] + sc["n2"]
     fc, B, sc_ = synth.make_params(1, 128, scale=5.0, seed=2)
     tfc = [torch.from_numpy(x).to(dev) for x in fc]
@@ -364,3 +352,69 @@ def test_gpu_sampler_twenty_objects_like_the_benchmarked_frame():
     for k, (sc, rnd) in enumerate(zip(scenes, rnds)):
         _check_against_oracle(got, k, _oracle(sc, rnd))
     _philox_checks({k: v.cpu().numpy() for k, v in outs[0][1].items()}, scenes)
+    sampler_checks.check_replay({k: v.cpu().numpy() for k, v in outs[0][1].items()}, scenes, 5, 2)     # every object draws its own counters
+
+
+# ---- Philox mode on the device, replayed: the kernel generates its numbers, philox_ref.frame_randoms + the oracle predict every output ----
+
+def _device_objects(scenes, dev):
+    import torch
+    return [dict(rgbs=torch.from_numpy(sc["rgbs"]).to(dev), depth=torch.from_numpy(sc["depth"]).to(dev),
+                 t_wc=torch.from_numpy(sc["t_wc"]).to(dev), bbox=torch.from_numpy(sc["bbox"]).to(dev),
+                 n_keyframes=sc["K"], last2=sc["last2"], center=sc["center"]) for sc in scenes]
+
+
+def _device_sampler(scenes, seed, dev="cuda:0", **kw):
+    from vmap_amd import sampler
+    s0 = scenes[0]
+    fx, fy, cx, cy = s0["intr"]
+    smp = sampler.FrameSampler(s0["W"], s0["H"], s0["F"], s0["P"], s0["n1"], s0["n2"], fx, fy, cx, cy, min_depth=s0["min_bound"],
+                               surface_eps=EPS, stop_eps=STOP, device=dev, seed=seed, **kw)
+    smp.set_objects(_device_objects(scenes, dev))
+    return smp
+
+
+def _host_frame(frame):
+    """A sampled frame as numpy arrays; a ray hand-off (step.RayPoints) rebuilt into the points tensor first."""
+    from vmap_amd import step
+    pcs = frame["pcs"].points(frame["z"]) if isinstance(frame["pcs"], step.RayPoints) else frame["pcs"]
+    return dict({k: v.cpu().numpy() for k, v in frame.items() if k != "pcs"}, pcs=pcs.cpu().numpy())
+
+
+def _replay_on_device(scenes, seed, frame_counter, **kw):
+    """One Philox-mode frame through FrameSampler(**kw), held to its replay; its figures are printed before anything is asserted."""
+    smp = _device_sampler(scenes, seed, **kw)
+    smp.frame_counter = frame_counter
+    out = _host_frame(smp.sample())
+    fig = sampler_checks.replay_figures(out, scenes, seed, frame_counter)
+    print(f"philox replay {kw} seed {seed:#x} frame {frame_counter}: max |dz| {fig[0]:.3g} |dpcs| {fig[1]:.3g} stratified |dz| {fig[2]:.3g}")
+    sampler_checks.check_replay(out, scenes, seed, frame_counter)
+    return fig
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rays", [False, True])
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("case", ["obj3", "S32", "S3_257rays"])
+def test_gpu_sampler_philox_mode_equals_its_replay(case, split, rays):
+    """Three objects; S = 32 (every u_z and normal stream, a sort without padding); S = 3 at 257 rays (a part-used quad, 14 pads, a
+    second trip of the thread loop, two slices in the split form): points and ray hand-off, split form and one workgroup per object."""
+    scenes, _, seed, c = sampler_checks.replay_scenes(case)
+    _replay_on_device(scenes, seed, c, split=split, rays=rays)
+
+
+@pytest.mark.gpu
+def test_gpu_sampler_philox_mode_uses_the_whole_seed_and_advances_its_frame_counter():
+    """seed = (5 << 32) | 9 through FrameSampler: the high word reaches the key.  Two sample() calls in a row, frame_counter
+    untouched between them: the replays at c and c + 1."""
+    scenes, _, seed, _ = sampler_checks.replay_scenes("bg_split4")
+    assert seed >> 32 == 5
+    smp = _device_sampler(scenes, seed)
+    smp.frame_counter = 6
+    first, second = _host_frame(smp.sample()), _host_frame(smp.sample())
+    assert smp.frame_counter == 8
+    sampler_checks.check_replay(first, scenes, seed, 6)
+    sampler_checks.check_replay(second, scenes, seed, 7)
+    low = _device_sampler(scenes, seed & 0xFFFFFFFF)
+    low.frame_counter = 6
+    assert (_host_frame(low.sample())["z"] != first["z"]).any(-1).mean() > 0.99
