@@ -422,6 +422,58 @@ int vmapstep_obb_extents(const float* points, int64_t n_points, const int64_t* o
 int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t* offsets, const int64_t* offsets_host, int32_t n_obj,
                            const float* center, double* moments, void* stream);
 
+/* ---- view rendering: every object field composited per pixel of a camera image --------------------------------------------------
+ * No counterpart in the reference (its vis.py only meshes); built from its ray convention (vmap.py:31-41, 507-516), its point
+ * arithmetic (vmap.py:452-454) and its compositing (render_rays.py:26-51).  Inputs: n_obj fields of hidden 32 with float32 weights
+ * (`params` + `pe_scale`, stacked as for the step); per object a box `boxes` [n_obj][15] = centre[3], R[9] (row-major, columns = the
+ * box's axes), full extent[3] (the layout of vmapstep_clip_box_*) and a field-frame centre `centers` [n_obj][3] (the object's
+ * obj_center, distinct from the box centre); the camera of vmapstep_view_cfg; images are [width][height] (width-major).  All DEVICE
+ * pointers except `offsets_host`.
+ *
+ * The contract.  float32 throughout; every fma below is one fused operation, everything else is rounded per operation (no
+ * contraction), divisions are IEEE.  Pixel (w, h), index p = w * height + h:  dc = ((w - cx) / fx, (h - cy) / fy, 1),
+ * d_i = fma(T[i][0], dc.x, fma(T[i][1], dc.y, T[i][2])), o = T[:, 3].  Box k: q = o - c, ob_i = fma(R[2][i], q.z, fma(R[1][i], q.y,
+ * R[0][i] * q.x)), db_i likewise from d, h_i = 0.5 * e_i, ta_i = (-h_i - ob_i) / db_i, tb_i = (h_i - ob_i) / db_i,
+ * t_near = fmaxf(min_depth, max_i fminf(ta_i, tb_i)), t_far = min_i fmaxf(ta_i, tb_i), fminf / fmaxf dropping a NaN operand; a hit
+ * iff t_far > t_near.  Samples of a hit: dt = (t_far - t_near) / samples, t_s = fma(s + 0.5f, dt, t_near), point = (o + d * t_s) -
+ * center_k; the field there gives occupancy sigmoid(10 * raw) and colour exactly as vmapstep_query_points does at hidden 32.
+ * Composite of a pixel: the samples of all boxes it hits in ascending (t, k); w_i = occ_i * prod_{j<i} ((1 - occ_j) + 1e-10f);
+ * depth = sum w_i t_i, colour = sum w_i c_i, opacity = sum w_i, accumulated in that order; instance = the object with the largest
+ * sum of its own w_i (ties: the smallest index), -1 where nothing is hit (depth, colour, opacity 0).  At most
+ * VMAPSTEP_VIEW_MAX_HITS boxes per pixel: with more, the VMAPSTEP_VIEW_MAX_HITS smallest by (t_near, k) are composited and the
+ * pixel adds one to `overflow` (DEVICE int32[1], which the caller zeroes; an ordinary atomic add).  Bit-identical from call to call
+ * and for any split of the pixel range [pix_begin, pix_end) into calls.
+ *
+ * vmapstep_view_count enqueues the count (one lane per pixel, one total per object and block of 64 pixels) and the scan, and writes
+ * `offsets` int64 [n_obj + 1] to DEVICE memory: the pairs (hits) of object k are [offsets[k], offsets[k + 1]).  The caller reads
+ * offsets[n_obj] (the one host synchronisation per call), allocates `pairs` (16 bytes per pair: int32 pixel, float32 t_near,
+ * float32 dt, int32 0; ordered by (object, pixel)), `sample_occ` float32 [n_pairs * samples] and `sample_rgb` float32
+ * [n_pairs * samples][3], and calls
+ * vmapstep_view_render with the same cfg, boxes and workspace, the offsets on the device and on the host (validated: from 0,
+ * non-decreasing, to n_pairs): it enqueues the parameter pack, the emit (nothing is written at or past n_pairs), the segmented
+ * field kernel and the composite, which writes depth, opacity float32 [width][height], color float32 [width][height][3] and
+ * instance int32 [width][height] at the pixels of the range.  The pair and sample buffers are outputs too.
+ * Limits, refused with VMAPSTEP_ERR_UNSUPPORTED before anything touches a device: hidden 32 only, 1 <= samples <= 64,
+ * 1 <= n_obj <= 256, 1 <= width, height <= 16384, n_pairs * samples < 2^31.  Workspace: 256-byte aligned,
+ * >= vmapstep_view_workspace_bytes(cfg) (VMAPSTEP_ERR_WORKSPACE otherwise); it depends on n_obj and the pixel range only. */
+#define VMAPSTEP_VIEW_MAX_HITS 16
+typedef struct vmapstep_view_cfg {
+    int32_t width, height, samples, n_obj;
+    float fx, fy, cx, cy;
+    float t_wc[16];                /* camera-to-world, row-major 4 x 4 */
+    float min_depth;
+    int64_t pix_begin, pix_end;    /* the pixels this call renders: [pix_begin, pix_end) of w * height + h */
+} vmapstep_view_cfg;
+
+int vmapstep_view_workspace_bytes(const vmapstep_view_cfg* cfg, size_t* bytes);
+int vmapstep_view_count(const vmapstep_view_cfg* cfg, const float* boxes, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vmapstep_params* params, const vmapstep_tensor* pe_scale,
+                         const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                         void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                         float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

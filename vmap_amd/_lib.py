@@ -96,6 +96,14 @@ class SurfaceRandoms(ctypes.Structure):
     _fields_ = [("u0", ctypes.c_void_p), ("r", ctypes.c_void_p)]
 
 
+class ViewCfg(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("samples", ctypes.c_int32), ("n_obj", ctypes.c_int32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("t_wc", ctypes.c_float * 16), ("min_depth", ctypes.c_float), ("pix_begin", ctypes.c_int64), ("pix_end", ctypes.c_int64)]
+
+
+VIEW_MAX_HITS = 16
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -107,7 +115,7 @@ EXPORTS = (
     "vmapstep_nn_workspace_bytes", "vmapstep_nn_distance", "vmapstep_surface_sample_workspace_bytes", "vmapstep_surface_sample",
     "vmapstep_clip_box_workspace_bytes", "vmapstep_clip_box_count", "vmapstep_clip_box_emit",
     "vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
-    "vmapstep_cloud_moments",
+    "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
 )
 
 _libs = {}
@@ -213,8 +221,15 @@ def load(path=None):
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.vmapstep_cloud_moments.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_view_workspace_bytes.argtypes = [ctypes.POINTER(ViewCfg), ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_view_count.argtypes = [ctypes.POINTER(ViewCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_view_render.argtypes = [ctypes.POINTER(ViewCfg), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Tensor),
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
-               "vmapstep_cloud_moments"):
+               "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_describe_plan", "vmapstep_param_layout", "vmapstep_workspace_bytes", "vmapstep_fwd_bwd", "vmapstep_render",
                "vmapstep_train_steps", "vmapstep_profile_main_kernel",

@@ -1,4 +1,5 @@
-// k_misc.hip - the kernels either side of the step: the inference query (query_kernels.h) and the
+// k_misc.hip - the kernels either side of the step: the inference query (query_kernels.h), its segmented
+// form for view rendering (field_query_seg_s32) and the
 // batched frame sampler (sample_kernels.h; row 1).  gfx950 only.
 #include "launch.h"
 #include "query_split_kernels.h"
@@ -37,6 +38,16 @@ int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, l
         }
     }
     return launched("field_query");
+}
+
+int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st) {
+    // every object's SPLIT image (step_prep_s32's pack role, zero mask-statistics blocks), then one workgroup per plan entry
+    hipLaunchKernelGGL(vk::step_prep_s32<>, dim3(a.n_obj * vk::kSplitPackBlocks), dim3(vk::kWG), 3 * vk::kWG * sizeof(int), st, pack);
+    if (int rc = launched("step_prep_s32")) return rc;
+    if (entries <= 0) return 0;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(vk::field_query_seg_s32<>), vk::kQuerySplitLds, "field_query_seg_s32")) return rc;
+    hipLaunchKernelGGL(vk::field_query_seg_s32<>, dim3((unsigned)entries), dim3(vk::kWG), vk::kQuerySplitLds, st, a);
+    return launched("field_query_seg_s32");
 }
 
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st) {

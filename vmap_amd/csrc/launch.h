@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include "query_kernels.h"
 #include "sample_kernels.h"
 #include "step_kernels.h"
+#include "view_args.h"
 
 namespace vk { struct WsArgs; }
 
@@ -55,6 +56,8 @@ int finalize_ws8(const vk::FinalizeArgs& f, const vk::FinalizeHot& h, const int*
 // k_misc.hip: inference query and the frame sampler
 int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, long long n_points, hipStream_t st);
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st);   // a.obj_max != null: the split form (two launches)
+// view rendering, the field pass: step_prep_s32's pack of all n_obj images, then field_query_seg_s32 over `entries` plan entries
+int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st);
 
 // The mesh, evaluation and bounds families below take their block sizes, workspace layouts and launch plans from launch_geometry.h
 // (vl::mesh_layout, nn_layout, nn_plan_host, surface_sample_bytes, clip_box_bytes, unproject_blocks, unproject_layout, obb_chunks).
@@ -95,5 +98,11 @@ int unproject_emit(const UnprojectFrames& f, const int* pairs, const int* first_
 int obb_extents(const float* points, const long long* po, int n_obj, const float* center, const float* rotations, long long set_stride,
                 int K, int chunks, float* lo, float* hi, hipStream_t st);
 int cloud_moments(const float* points, const long long* po, int n_obj, const float* center, double* moments, hipStream_t st);
+
+
+// k_view.hip: view rendering (view_kernels.h).  The workspace is vl::view_layout's; ViewArgs carries its sections.
+int view_count(const vv::ViewArgs& a, hipStream_t st);                           // view_count, view_scan -> a.offsets
+int view_emit(const vv::ViewArgs& a, hipStream_t st);                            // view_emit, view_plan (a.plan_per from view_plan_host)
+int view_composite(const vv::ViewArgs& a, hipStream_t st);
 
 }  // namespace vl

@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation and bounds families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds and view families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -28,6 +28,17 @@ constexpr int kObbCand = 4;                // candidates per lane
 constexpr int kObbBlock = kBoundsWG * kObbCand;   // candidates per block
 constexpr int kObbTile = 512;              // points per LDS tile (float4 each: 8 KiB)
 }  // namespace vb
+
+namespace vv {
+constexpr int kViewBlock = 64;             // pixels per block of view_count / _emit / _composite: one wave, one lane per pixel
+constexpr int kViewScanWG = 1024;          // view_scan
+constexpr int kViewPlanWG = 256;           // view_plan: one lane per object (n_obj <= kViewMaxObj)
+constexpr int kViewMaxObj = 256;
+constexpr int kViewMaxHits = 16;           // VMAPSTEP_VIEW_MAX_HITS
+constexpr int kViewMaxSamples = 64;
+constexpr int kViewChunk = 128;            // points per chunk of field_query_seg_s32 (four waves x 32-point tiles)
+constexpr int kViewImgBytes = 81920;       // one object's split image (vk::Img32s::BYTES; asserted where both are visible)
+}  // namespace vv
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -116,6 +127,40 @@ inline int obb_chunks(const long long* po, int n_obj, int K) {
     long long c = ceil_div(kObbBlocksTarget, per_chunk);
     c = c > tiles ? tiles : c;
     return (int)(c < 1 ? 1 : c > 65535 ? 65535 : c);
+}
+
+// View rendering.  The workspace of a call over the pixels [pix_begin, pix_end): the split parameter image of every object
+// (n_obj x vv::kViewImgBytes, packed by step_prep_s32), one int64 per (object, block of vv::kViewBlock pixels) - the hits of the
+// block, then (after view_scan) their exclusive prefix in (object, block) order - and the launch plan of field_query_seg_s32.
+inline int view_blocks(long long pix_begin, long long pix_end) { return (int)ceil_div(pix_end - pix_begin, vv::kViewBlock); }
+struct ViewLayout {
+    size_t off_blk, off_plan, bytes;
+};
+constexpr long long kViewWgTarget = 512;                                  // two workgroups per compute unit (2 x 80 KiB of LDS)
+constexpr long long kViewPlanCap = kViewWgTarget + vv::kViewMaxObj;       // entries the plan can hold (every object rounds up once)
+inline ViewLayout view_layout(int n_obj, long long pix_begin, long long pix_end) {
+    ViewLayout l;
+    l.off_blk = ws_up((size_t)n_obj * vv::kViewImgBytes);
+    l.off_plan = l.off_blk + ws_up((size_t)n_obj * view_blocks(pix_begin, pix_end) * sizeof(long long));
+    l.bytes = l.off_plan + ws_up((size_t)kViewPlanCap * 4 * sizeof(int));
+    return l;
+}
+// The launch plan of field_query_seg_s32 from the host copy of the pair offsets: one entry (object, first chunk, end chunk) per
+// workgroup, chunks of vv::kViewChunk points, `per` chunks per workgroup chosen so that about kViewWgTarget workgroups exist;
+// view_plan writes the entries on the device by the same formula.  The output does not depend on the plan (a point's value
+// depends on the point alone).
+struct ViewPlan {
+    long long per, entries;
+};
+inline ViewPlan view_plan_host(const long long* offsets, int n_obj, int samples) {
+    long long chunks = 0;
+    for (int k = 0; k < n_obj; ++k) chunks += ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk);
+    ViewPlan p;
+    p.per = ceil_div(chunks, kViewWgTarget);
+    p.per = p.per < 1 ? 1 : p.per;
+    p.entries = 0;
+    for (int k = 0; k < n_obj; ++k) p.entries += ceil_div(ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk), p.per);
+    return p;
 }
 
 }  // namespace vl

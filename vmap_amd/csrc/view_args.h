@@ -1,0 +1,27 @@
+// view_args.h - the argument block of the view kernels (view_kernels.h: view_count, view_scan, view_emit, view_plan, view_composite;
+// query_split_kernels.h: field_query_seg_s32).  Plain C++: the C ABI unit fills it, the two kernel units launch with it.
+#pragma once
+#include "view_geometry.h"
+
+namespace vv {
+
+struct ViewArgs {
+    vg::Camera cam;
+    int n_obj, nb;                         // nb = blocks of kViewBlock pixels in [pix_begin, pix_end)
+    long long pix_begin, pix_end;          // the call's pixel range (pixel index w * height + h)
+    const float* boxes;                    // [n_obj][15] centre, R (row-major, columns = axes), full extent
+    const float* centers;                  // [n_obj][3] field-frame centres
+    const float* scale; long long scale_so;   // pe.scale of object k = scale[k * scale_so]
+    const char* wimg;                      // workspace: [n_obj] split images (Img32s)
+    long long* blk;                        // workspace: [n_obj * nb] hits per block, then their exclusive prefix
+    int* plan;                             // workspace: [entries][4] (object, first chunk, end chunk, 0)
+    long long plan_per;                    // chunks per plan entry
+    long long* offsets;                    // [n_obj + 1] pair offsets
+    vg::Pair* pairs; long long cap;        // [cap] pair records, ordered by (object, pixel)
+    float* occ;                            // [cap * samples]
+    float* rgb;                            // [cap * samples][3]
+    float* depth; float* color; float* opacity; int* instance;      // [width * height] (x 3)
+    int* overflow;                         // [1] pixels that hit more than kViewMaxHits boxes (added to)
+};
+
+}  // namespace vv

@@ -1075,6 +1075,101 @@ int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t*
 
 static_assert(sizeof(vmapstep_sample_object) == sizeof(vs::SampleObject), "sample object table layout");
 
+// ---- view rendering ----------------------------------------------------------------------------------------------------------------
+static int check_view_cfg(const vmapstep_view_cfg* c) {
+    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "view: cfg is null");
+    if (c->samples < 1 || c->samples > vv::kViewMaxSamples || c->n_obj < 1 || c->n_obj > vv::kViewMaxObj || c->width < 1 || c->height < 1 ||
+        c->width > 16384 || c->height > 16384)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: 1 <= samples <= %d, 1 <= n_obj <= %d, 1 <= width, height <= 16384 (samples=%d n_obj=%d width=%d height=%d)",
+                    vv::kViewMaxSamples, vv::kViewMaxObj, c->samples, c->n_obj, c->width, c->height);
+    if (c->pix_begin < 0 || c->pix_end < c->pix_begin || c->pix_end > (int64_t)c->width * c->height)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "view: pixel range [%lld, %lld) outside the image", (long long)c->pix_begin, (long long)c->pix_end);
+    if (!(std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy)) || c->fx == 0.0f || c->fy == 0.0f)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "view: intrinsics must be finite with fx, fy != 0");
+    return VMAPSTEP_OK;
+}
+
+static int check_view_workspace(const vmapstep_view_cfg* c, void* workspace, size_t workspace_bytes) {
+    const size_t need = vl::view_layout(c->n_obj, c->pix_begin, c->pix_end).bytes;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "view workspace must be 256-byte aligned and >= %zu bytes", need);
+    return VMAPSTEP_OK;
+}
+
+static vv::ViewArgs view_args(const vmapstep_view_cfg* c, const float* boxes, void* workspace) {
+    vv::ViewArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.cam.fx = c->fx; a.cam.fy = c->fy; a.cam.cx = c->cx; a.cam.cy = c->cy;
+    std::memcpy(a.cam.T, c->t_wc, sizeof(a.cam.T));
+    a.cam.min_depth = c->min_depth; a.cam.width = c->width; a.cam.height = c->height; a.cam.samples = c->samples;
+    a.n_obj = c->n_obj; a.pix_begin = c->pix_begin; a.pix_end = c->pix_end; a.nb = vl::view_blocks(c->pix_begin, c->pix_end);
+    a.boxes = boxes;
+    const vl::ViewLayout l = vl::view_layout(c->n_obj, c->pix_begin, c->pix_end);
+    char* ws = static_cast<char*>(workspace);
+    a.wimg = ws;
+    a.blk = reinterpret_cast<long long*>(ws + l.off_blk);
+    a.plan = reinterpret_cast<int*>(ws + l.off_plan);
+    return a;
+}
+
+int vmapstep_view_workspace_bytes(const vmapstep_view_cfg* cfg, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_view_cfg(cfg)) return rc;
+    *bytes = vl::view_layout(cfg->n_obj, cfg->pix_begin, cfg->pix_end).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_view_count(const vmapstep_view_cfg* cfg, const float* boxes, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (int rc = check_view_cfg(cfg)) return rc;
+    if (!boxes || !offsets) return fail(VMAPSTEP_ERR_ARGUMENT, "view: null argument");
+    if (int rc = check_view_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    vv::ViewArgs a = view_args(cfg, boxes, workspace);
+    a.offsets = reinterpret_cast<long long*>(offsets);
+    return vl::view_count(a, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vmapstep_params* params, const vmapstep_tensor* pe_scale,
+                         const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                         void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                         float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (hidden != 32) return fail(VMAPSTEP_ERR_UNSUPPORTED, "view: hidden=%d, the view renderer implements hidden 32 only", hidden);
+    if (int rc = check_view_cfg(cfg)) return rc;
+    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "view: n_pairs=%lld", (long long)n_pairs);
+    if (n_pairs * cfg->samples >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: n_pairs * samples < 2^31 (n_pairs=%lld samples=%d): render the pixel range in bands",
+                    (long long)n_pairs, cfg->samples);
+    if (int rc = check_params(params, "params", false)) return rc;
+    if (!pe_scale || !pe_scale->ptr || !boxes || !centers || !offsets || !offsets_host || !depth || !color || !opacity || !instance || !overflow ||
+        (n_pairs > 0 && (!pairs || !sample_occ || !sample_rgb)))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "view: null argument");
+    if (offsets_host[0] != 0 || offsets_host[cfg->n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "view: offsets must run from 0 to n_pairs");
+    for (int32_t k = 0; k < cfg->n_obj; ++k)
+        if (offsets_host[k + 1] < offsets_host[k]) return fail(VMAPSTEP_ERR_ARGUMENT, "view: offsets decrease at object %d", (int)k);
+    if (int rc = check_view_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    vv::ViewArgs a = view_args(cfg, boxes, workspace);
+    a.centers = centers; a.scale = pe_scale->ptr; a.scale_so = pe_scale->obj_stride;
+    a.offsets = const_cast<long long*>(reinterpret_cast<const long long*>(offsets));
+    a.pairs = static_cast<vg::Pair*>(pairs); a.cap = n_pairs;
+    a.occ = sample_occ; a.rgb = sample_rgb;
+    a.depth = depth; a.color = color; a.opacity = opacity; a.instance = instance; a.overflow = overflow;
+    const vl::ViewPlan plan = vl::view_plan_host(reinterpret_cast<const long long*>(offsets_host), cfg->n_obj, cfg->samples);
+    a.plan_per = plan.per;
+    if (int rc = vl::view_emit(a, st)) return rc;
+    vk::StepArgs pk;
+    std::memset(&pk, 0, sizeof(pk));
+    pk.n_obj = cfg->n_obj; pk.hidden = 32; pk.prep_steps = 0;
+    for (int t = 0; t < VMAPSTEP_NUM_FC; ++t) pk.fc[t] = {params->fc[t].ptr, params->fc[t].obj_stride};
+    pk.pe_B = {params->pe_B.ptr, params->pe_B.obj_stride};
+    pk.wimg = static_cast<float*>(workspace);
+    if (int rc = vl::view_field(pk, a, plan.entries, st)) return rc;
+    return vl::view_composite(a, st);
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

@@ -185,6 +185,14 @@ class HipMapper:
         res_bg.flags.record_stream(cur)
         return res, res_bg
 
+    # ---- looking at the map -----------------------------------------------------------------------------------
+    def render_view(self, boxes, t_wc, intrinsics, width, height, centers=None, **kw):
+        """Depth, colour, opacity and instance images of the object stack from the camera-to-world pose ``t_wc``: ``render.render_view``
+        over the live slab (no copy).  ``boxes`` / ``centers``: one box (``None`` = skip the object) and one ``obj_center`` per object,
+        in ``add_object`` order; the keywords are ``render_view``'s (samples, min_depth, pixel_range, budget_bytes, return_samples)."""
+        from . import render
+        return render.render_view(self, boxes, t_wc, intrinsics, width, height, centers=centers, **kw)
+
     def check_flags(self, res: step.StepResult):
         """Host-side look at the device flags of a frame (the reference exits on 'loss explode', render_rays.py:88-90)."""
         f = res.flags.cpu()
