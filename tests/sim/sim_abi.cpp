@@ -1,36 +1,58 @@
 // TEST INFRASTRUCTURE: runs the kernels of vmap_amd/csrc/step_kernels.h on the CPU SIMT executor.
-// Host pointers in, host pointers out; mirrors the launch sequence of vmap_amd/csrc/vmapstep.hip.
+// Host pointers in, host pointers out.  The step's layout, plan, workspace sections, argument blocks and finalize route are the
+// product's own (vmap_amd/csrc/step_plan.h, the text vmapstep.hip compiles); what a test forces on purpose is said where it enters.
+#include <cstdarg>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include <cmath>
 
 #include "sim_launch.h"
+#include "step_plan.h"
 
 namespace {
-void fc_sizes(int H, int* sz) {
-    const int s[14] = {H * 87, H, H * H, H, H * (H + 87), H, H * H, H, H, 1, H * (H + 42), H, 3 * H, 3};
-    for (int i = 0; i < 14; ++i) sz[i] = s[i];
+thread_local char g_err[512] = "";
 }
-}  // namespace
+int vl::fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
 
 extern "C" int vmsim_lds_bytes() { return vk::Lds32::BYTES; }
 static int g_fin_form = 0;   // step_finalize_ws: 0 = a thread per quad and row group (what small shapes get), 1 = one thread per quad (many blocks / few rows)
 extern "C" void vmsim_set_finalize_form(int f) { g_fin_form = f; }
-static int g_wide = 0;
-extern "C" void vmsim_set_wide(int w) { g_wide = w; }
 static int g_sample_split = 0;
 extern "C" void vmsim_set_sample_split(int nsplit) { g_sample_split = nsplit; }   // > 1: the split form of the sampler (two launches)
 // ABI v7 ray hand-off: when set, the next vmsim_step ignores `pcs` and hands the kernels origin / direction [n][R][3] + centres [n][3]
 static const float* g_ray_o = nullptr; static const float* g_ray_d = nullptr; static const float* g_ray_c = nullptr;
 extern "C" void vmsim_set_rays(const float* o, const float* d, const float* c) { g_ray_o = o; g_ray_d = d; g_ray_c = c; }
 extern "C" void vmsim_set_schedule(int s) { sim::set_schedule(s); }   // 0 round-robin (default), 1 / 2 wave-greedy forward / reverse (sim_runtime.h)
-static int g_split = 0;
-extern "C" void vmsim_set_split(int on) { g_split = on; }   // hidden 32: 1 = step_main_s32 (split-bf16 matrix pipe) instead of step_main_h32; 2 = ... with the six-product backward   
 
-// fc[t]: [n][size_t] contiguous; grads: flat slab [n][P] in natural order (14 field tensors then B).
-extern "C" int vmsim_step(int n, int R, int S, int H, int G, int NW_req, int xcd_affine, int weights_bf16,
+// The plan the product makes for a shape (vl::make_plan, with or without the measurement build's forms) -> status; msg: the refusal's
+// text; out: family, G, tiles, NG, NW, PR, xcd_affine of the main kernel and of the finalize, the nine section offsets, the total
+extern "C" int vmsim_step_plan(const vmapstep_shape* sh, int max_steps, int measurement_build, long long out[18], char* msg, int msg_len) {
+    vl::Layout L;
+    vl::Plan pl;
+    if (sh) vl::make_layout(sh->hidden, L);
+    const int rc = vl::make_plan(sh, max_steps, measurement_build != 0, L, pl);
+    std::snprintf(msg, msg_len, "%s", rc ? g_err : "");
+    if (rc) return rc;
+    vk::StepArgs a;
+    vl::fill_step_plan(a, sh, pl, L);
+    const long long v[18] = {pl.family, pl.G, pl.tiles, pl.NG, pl.NW, pl.PR, a.xcd_affine, vl::finalize_xcd_affine(a, true),
+                             (long long)pl.off_ploss, (long long)pl.off_imgtab, (long long)pl.off_tab_wt, (long long)pl.off_row_tab, (long long)pl.off_pgrad,
+                             (long long)pl.off_wimg, (long long)pl.off_scratch, (long long)pl.off_flags, (long long)pl.off_stats, (long long)pl.total};
+    std::memcpy(out, v, sizeof(v));
+    return 0;
+}
+
+// family: vl::Family.  fc[t]: [n][size_t] contiguous; grads: flat slab [n][P] in natural order (14 field tensors then B).
+extern "C" int vmsim_step(int n, int R, int S, int H, int family, int G, int NW_req, int xcd_affine, int weights_bf16,
                           const float* const* fc, const float* B, const float* scale,
                           const float* pcs, const float* z, const float* gt_depth, const float* gt_rgb,
                           const uint8_t* sem, const uint8_t* dmask, float color_w, float opac_w,
@@ -38,119 +60,90 @@ extern "C" int vmsim_step(int n, int R, int S, int H, int G, int NW_req, int xcd
                           float* dbg_var, int* flags, int bwd,
                           // optional fused AdamW (params updated in copies p_out [n][P], moments m, v [n][PP])
                           int do_adam, float* p_out, float* m, float* v, int step, float lr, float wd) {
-    if (H % 32 != 0 || H < 32 || H > 256) return -1;
+    const vl::Family fam = (vl::Family)family;
+    if (H % 32 != 0 || H < 32 || H > 256 || vl::hidden32(fam) != (H == 32)) return -1;
     if (G * S > vk::kMaxPts || G < 1) return -2;
-    int sz[14], offs[16];
-    fc_sizes(H, sz);
-    int P = 0;
-    for (int t = 0; t < 14; ++t) { offs[t] = P; P += sz[t]; }
-    offs[14] = P; P += 63; offs[15] = P;
-    const int PP = (P + 63) / 64 * 64;
-    const int NG = (R + G - 1) / G;
-    const int NW = NW_req > 0 && NW_req < NG ? NW_req : NG;
+    vl::Layout L;
+    vl::make_layout(H, L);
+    const vmapstep_tuning tun = {NW_req, VMAPSTEP_KERNEL_AUTO, 0, 0};
+    const vmapstep_shape sh = {n, R, S, H, weights_bf16, 0, &tun};
+    vl::Plan pl;
+    pl.family = fam;
+    if (vl::check_shape(&sh, 1) || vl::plan_rounds(&sh, true, pl)) return -4;
+    // What the tests force, over the plan's rounds: G rays per round as they are given (also more than the object has), for
+    // step_main_ws the fewest 32-point tiles that hold them, and NW_req workgroups per object (0: one per round)
+    pl.G = G;
+    pl.tiles = fam == vl::kWs ? (G * S <= 32 ? 1 : G * S <= 64 ? 2 : 3) : 2;
+    if (G * S > vl::round_points(fam, pl.tiles) || (fam == vl::kWs && pl.tiles > (H == 256 ? 1 : H == 128 ? 3 : 2))) return -3;
+    pl.NG = (R + G - 1) / G;
+    pl.NW = NW_req > 0 && NW_req < pl.NG ? NW_req : pl.NG;
+    if (vl::plan_sections(&sh, 1, L, pl)) return -4;
 
-    std::vector<int> fl(4, -1);
-    const vk::GenLayout GL = vk::gen_layout(H);
-    const bool split = g_split && H == 32;
-    const bool wp = g_wide == 4 && (H == 128 || H == 64);    // step_main_wp (two waves per output block)
-    const bool ws = ((g_wide == 3 || g_wide == 4) && (H == 128 || H == 64)) || (g_wide == 3 && H == 256);    // step_main_ws / _wp (split-bf16 matrix pipe, hidden 128 / 64; _ws also 256)
-    const int PR = ws ? vk::ws_row_floats(H) : PP;          // floats per row of partial gradients (step_main_ws / _wp: block-native rows)
-    std::vector<float> stats(n * 4, NAN), part_grad((size_t)n * NW * PR, NAN), part_loss((size_t)n * NW * 4, NAN);
-    std::vector<int> row_tab(PR, -7);
-    if (ws && G * S > (H == 256 ? 32 : g_wide == 3 && H == 128 ? 96 : vk::ImgWs<4>::kPts)) return -3;   // step_main_ws at hidden 128: up to three 32-point tiles per round
-    std::vector<float> wimg((size_t)n * (split ? vk::Img32s::BYTES / 4 : ws ? (H == 256 ? vk::ImgWs<8>::BYTES : H == 128 ? vk::ImgWs<4>::BYTES : vk::ImgWs<2>::BYTES) / 4 : GL.imgp), NAN);
+    // one workspace, every section poisoned: -1 tables and flags, 0xFF scratch, NaN floats, -7 in the row table
+    std::vector<char> buf(pl.total + vl::kAlign, (char)0xFF);
+    char* ws = buf.data() + (vl::kAlign - reinterpret_cast<uintptr_t>(buf.data()) % vl::kAlign) % vl::kAlign;
+    auto poison = [&](size_t from, size_t to, auto value) { std::fill((decltype(value)*)(ws + from), (decltype(value)*)(ws + to), value); };
+    poison(pl.off_ploss, pl.off_imgtab, (float)NAN);
+    poison(pl.off_row_tab, pl.off_pgrad, -7);
+    poison(pl.off_pgrad, pl.off_scratch, (float)NAN);
+    poison(pl.off_stats, pl.total, (float)NAN);
 
-    vk::StepArgs a{};
-    a.tiles = g_wide == 3 ? (G * S <= 32 ? 1 : G * S <= 64 ? 2 : 3) : 2;   // step_main_ws: the fewest 32-point tiles that hold the caller's ray groups
-    a.n_obj = n; a.R = R; a.S = S; a.G = G; a.NG = NG; a.NW = NW; a.PP = PP; a.PR = PR; a.row_tab = ws ? row_tab.data() : nullptr; a.prep_steps = 1; a.prep_ray_step = 0; a.xcd_affine = (xcd_affine && H == 32) ? 1 : 0; a.hidden = H; a.weights_bf16 = weights_bf16;
-    for (int t = 0; t < 14; ++t) a.fc[t] = {const_cast<float*>(fc[t]), sz[t]};
-    a.pe_B = {const_cast<float*>(B), 63};
-    a.pe_scale = {const_cast<float*>(scale), 1};
-    a.pcs = pcs; a.pcs_so = (long long)R * S * 3; a.pcs_sr = S * 3; a.pcs_ss = 3; a.pcs_sc = 1;
-    if (g_ray_o) {
-        a.pcs = nullptr;
-        a.ray_o = g_ray_o; a.ro_so = (long long)R * 3; a.ro_sr = 3; a.ro_sc = 1;
-        a.ray_d = g_ray_d; a.rd_so = (long long)R * 3; a.rd_sr = 3; a.rd_sc = 1;
-        a.center = g_ray_c; a.ce_so = 3;
-    }
-    a.z = z; a.z_so = (long long)R * S; a.z_sr = S; a.z_ss = 1;
-    a.gt_depth = gt_depth; a.gd_so = R; a.gd_sr = 1;
-    a.gt_rgb = gt_rgb; a.rgb_so = R * 3; a.rgb_sr = 3; a.rgb_sc = 1;
-    a.sem = sem; a.sem_so = R; a.sem_sr = 1;
-    a.dmask = dmask; a.dm_so = R; a.dm_sr = 1;
-    a.color_w = color_w; a.opac_w = opac_w;
-    a.stats = stats.data(); a.flags = fl.data();
-    a.part_grad = part_grad.data(); a.part_loss = part_loss.data(); a.wimg = wimg.data();
-    a.dbg_depth = dbg_depth; a.dbg_rgb = dbg_rgb; a.dbg_opacity = dbg_opacity; a.dbg_var = dbg_var;
-    std::vector<int> img_tab(PP, -1);
-    a.img_tab = H == 32 || ws ? img_tab.data() : nullptr;   // flat parameter -> image position (step_finalize_h32)
-    std::vector<int> tab_wt(PP, -1);
-    vk::WsArgs wa{};
-
-    std::vector<char> ws_scratch;
-    if (ws) {
-        ws_scratch.assign((size_t)n * NW * (wp ? (H == 128 ? vk::LdsWp<4>::WG_SCRATCH : vk::LdsWp<2>::WG_SCRATCH) : (size_t)vk::kWsScratchMax), (char)0xFF);
-        wa.s = a; wa.scratch = ws_scratch.data(); wa.tab_wt = tab_wt.data();
-        sl::prep_ws(wa);
-    } else if (split) sl::prep_s32(a);
-    else sl::prep_f32(a, 1 + n * (vk::gen_layout(H).imgp / 1024));
-    if (wp) sl::main_wp(wa, bwd);
-    else if (ws) sl::main_ws(wa, bwd);
-    else if (split) { a.bwd6 = (g_split == 2 && bwd && !weights_bf16) ? 1 : 0; sl::main_s32(a, bwd); }
-    else if (int rc = sl::main_f32(a, g_wide, bwd, G)) return rc;
-
-    vk::FinalizeArgs f{};
-    f.n_obj = n; f.NW = NW; f.PP = PP; f.P = P; f.hidden = H; f.weights_bf16 = weights_bf16;
-    f.PR = PR; f.row_tab = a.row_tab;
-    for (int t = 0; t < 16; ++t) f.offs[t] = offs[t];
+    vmapstep_params params, outs, gouts;
     for (int t = 0; t < 15; ++t) {
-        f.grad[t] = {grads ? grads + offs[t] : nullptr, P};
-        f.param[t] = {p_out ? p_out + offs[t] : nullptr, P};
+        (t < 14 ? params.fc[t] : params.pe_B) = {const_cast<float*>(t < 14 ? fc[t] : B), L.sizes[t]};
+        (t < 14 ? outs.fc[t] : outs.pe_B) = {p_out ? p_out + L.offs[t] : nullptr, L.P};
+        (t < 14 ? gouts.fc[t] : gouts.pe_B) = {grads ? grads + L.offs[t] : nullptr, L.P};
     }
-    f.m = m; f.v = v; f.wimg = wimg.data();
-    f.part_grad = part_grad.data(); f.have_grad = bwd;
-    f.part_loss = part_loss.data();
-    f.flags_in = fl.data(); f.flags_out = flags; f.loss_out = loss;
-    f.color_w = color_w; f.opac_w = opac_w;
-    f.do_adam = do_adam;
-    f.decay = (float)(1.0 - (double)lr * (double)wd);
-    f.one_minus_beta1 = (float)(1.0 - 0.9); f.beta2 = 0.999f; f.one_minus_beta2 = (float)(1.0 - 0.999);
-    f.eps = 1e-8f;
-    f.step_size = (float)((double)lr / (1.0 - std::pow(0.9, step)));
-    f.bias_corr2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, step));
-    const int bpo = (PP / 4 + vk::kWG - 1) / vk::kWG;
-    if (ws && bwd) {
-        // one finalize for the gradients the tests look at and / or the AdamW update (as the library launches it)
-        vk::FinalizeHot h{};
-        h.m = f.m; h.v = f.v; h.part_grad = f.part_grad; h.wimg = f.wimg; h.img_tab = img_tab.data();
-        h.NW = f.NW; h.PP = f.PP; h.PR = f.PR; h.weights_bf16 = f.weights_bf16;
-        h.decay = f.decay; h.one_minus_beta1 = f.one_minus_beta1; h.beta2 = f.beta2; h.one_minus_beta2 = f.one_minus_beta2;
-        h.eps = f.eps; h.step_size = f.step_size; h.bias_corr2_sqrt = f.bias_corr2_sqrt;
-        f.do_adam = do_adam && p_out;
-        f.ws_grouped = g_fin_form == 0;
-        sl::finalize_ws(f, h, tab_wt.data());
-        return 0;
+    const vmapstep_tensor pe_scale = {const_cast<float*>(scale), 1};
+    vmapstep_batch b = {};
+    b.pcs = pcs; b.pcs_stride[0] = (long long)R * S * 3; b.pcs_stride[1] = S * 3; b.pcs_stride[2] = 3; b.pcs_stride[3] = 1;
+    if (g_ray_o) {
+        b.pcs = nullptr;
+        b.ray_o = g_ray_o; b.ray_o_stride[0] = (long long)R * 3; b.ray_o_stride[1] = 3; b.ray_o_stride[2] = 1;
+        b.ray_d = g_ray_d; b.ray_d_stride[0] = (long long)R * 3; b.ray_d_stride[1] = 3; b.ray_d_stride[2] = 1;
+        b.center = g_ray_c; b.center_stride = 3;
     }
-    if (H == 32 && bwd && do_adam && p_out) {
-        // the table-driven form the library launches for a plain training step at hidden 32 (parameters: one [n, P] slab here);
-        // the gradients the tests look at come from a gradient-only pass of the generic kernel first
-        if (grads) {
-            vk::FinalizeArgs fg = f;
-            fg.do_adam = 0;
-            sl::finalize_generic(fg, n * bpo + 1);
-            for (int t = 0; t < 15; ++t) f.grad[t] = {nullptr, P};
-        }
-        vk::FinalizeHot h{};
-        h.m = f.m; h.v = f.v; h.part_grad = f.part_grad; h.wimg = f.wimg; h.img_tab = img_tab.data();
-        h.slab = p_out; h.slab_stride = P;
-        h.NW = f.NW; h.PP = f.PP; h.PR = f.PR; h.weights_bf16 = f.weights_bf16;
-        h.decay = f.decay; h.one_minus_beta1 = f.one_minus_beta1; h.beta2 = f.beta2; h.one_minus_beta2 = f.one_minus_beta2;
-        h.eps = f.eps; h.step_size = f.step_size; h.bias_corr2_sqrt = f.bias_corr2_sqrt;
-        if (split) sl::finalize_s32(f, h, n * bpo + 1);
-        else sl::finalize_h32(f, h, n * bpo + 1);
-        return 0;
-    }
-    sl::finalize_generic(f, n * bpo + 1);
+    b.z = z; b.z_stride[0] = (long long)R * S; b.z_stride[1] = S; b.z_stride[2] = 1;
+    b.gt_depth = gt_depth; b.gt_depth_stride[0] = R; b.gt_depth_stride[1] = 1;
+    b.gt_rgb = gt_rgb; b.gt_rgb_stride[0] = R * 3; b.gt_rgb_stride[1] = 3; b.gt_rgb_stride[2] = 1;
+    b.sem = sem; b.sem_stride[0] = R; b.sem_stride[1] = 1;
+    b.depth_mask = dmask; b.depth_mask_stride[0] = R; b.depth_mask_stride[1] = 1;
+
+    vk::StepArgs a;
+    vl::fill_step_args(a, &sh, pl, L, &params, &pe_scale, &b, 0, color_w, opac_w, ws);
+    a.prep_steps = 1; a.prep_ray_step = 0;
+    if (H == 32) a.xcd_affine = xcd_affine ? 1 : 0;        // hidden 32: the block map the test asks for, whatever the workgroup count
+    a.dbg_depth = dbg_depth; a.dbg_rgb = dbg_rgb; a.dbg_opacity = dbg_opacity; a.dbg_var = dbg_var;
+    vk::WsArgs wa{};
+    wa.s = a; wa.scratch = reinterpret_cast<char*>(a.gen_scratch); wa.tab_wt = a.tab_wt;
+
+    if (vl::block_native_rows(fam)) sl::prep_ws(wa);
+    else if (a.split) sl::prep_s32(a);
+    else sl::prep_f32(a, vl::prep_f32_blocks(a, 1));
+    if (fam == vl::kWp) sl::main_wp(wa, bwd);
+    else if (fam == vl::kWs) sl::main_ws(wa, bwd);
+    else if (a.split) sl::main_s32(a, bwd);
+    else if (int rc = sl::main_f32(a, a.wide, bwd, G)) return rc;
+
+    vk::FinalizeArgs f;
+    const bool adam = do_adam && p_out;
+    vl::fill_finalize_args(f, a, L, &outs, grads ? &gouts : nullptr, adam ? m : nullptr, adam ? v : nullptr, bwd != 0, loss, flags, nullptr);
+    if (f.do_adam) vl::adamw_consts(f, lr, 0.9, 0.999, 1e-8f, wd, step);
+    vl::FinalizeRoute route = vl::finalize_route(a, f, grads != nullptr, false);
+    bool grad_pass = route == vl::kFinS32AfterGrads;
+    // the tests look at the gradients AND at the table-driven update of step_finalize_h32: it gets the gradient-only pass that the
+    // product launches in front of step_finalize_s32 (the product itself would take step_finalize for both)
+    if (fam == vl::kH32 && f.do_adam && grads) { route = vl::kFinH32; grad_pass = true; }
+    const int grid = vl::finalize_grid(f);
+    if (route == vl::kFinGeneric) { sl::finalize_generic(f, grid); return 0; }
+    if (grad_pass) sl::finalize_generic(vl::split_off_grad_pass(f), grid);
+    vk::FinalizeHot h;
+    vl::fill_hot(h, f, a, L, &outs);
+    if (route == vl::kFinWs) {
+        f.ws_grouped = g_fin_form == 0;          // the form the test asks for
+        sl::finalize_ws(f, h, a.tab_wt);
+    } else if (route == vl::kFinH32) sl::finalize_h32(f, h, grid);
+    else sl::finalize_s32(f, h, grid);
     return 0;
 }
 

@@ -64,7 +64,6 @@ void main_ws_t(const vk::WsArgs& wa, bool bwd) {
 void finalize_ws(const vk::FinalizeArgs& f_in, const vk::FinalizeHot& h, const int* tab_wt) {
     vk::FinalizeArgs f = f_in;
     f.loss_stage = vk::loss_stage_cap(vk::kFinThreads * 16);
-    f.xcd_affine = f.n_obj >= 8 ? 1 : 0;          // as the library's launcher
     const int grid = vk::ws_finalize_grid(f.n_obj, f.PR, vk::kFinQuads, f.xcd_affine);
     if (f.hidden == 256) return finalize_ws8(f, h, tab_wt, grid);
     if (!f.ws_grouped) {            // the form the library's launcher picks for many blocks / few rows (here: on request)

@@ -87,6 +87,21 @@ def _p(a, ty=ctypes.c_float):
     return a.ctypes.data_as(ctypes.POINTER(ty)) if a is not None else None
 
 
+FAMILIES = ("h32", "s32", "s32_bwd6", "gen", "wide", "ws", "wp")      # vl::Family, in its order
+
+
+def step_plan(shape, max_steps, measurement_build):
+    """The plan vl::make_plan (csrc/step_plan.h, as the executor library compiles it) makes for a vmap_amd._lib.Shape:
+    -> (status, message, dict of family, G, tiles, NG, NW, PR, xcd_main, xcd_finalize, the section offsets and total - or None)"""
+    out, msg = (ctypes.c_longlong * 18)(), ctypes.create_string_buffer(512)
+    rc = lib().vmsim_step_plan(ctypes.byref(shape), int(max_steps), int(measurement_build), out, msg, len(msg))
+    return rc, msg.value.decode(), None if rc else dict(zip(PLAN_FIELDS, out), family=FAMILIES[out[0]])
+
+
+PLAN_FIELDS = ("family", "G", "tiles", "NG", "NW", "PR", "xcd_main", "xcd_finalize", "off_ploss", "off_imgtab", "off_tab_wt", "off_row_tab",
+               "off_pgrad", "off_wimg", "off_scratch", "off_flags", "off_stats", "total")
+
+
 def sim_step(case_or_fc, B=None, scale=None, batch=None, G=None, bwd=True, adam=None, NW=0, xcd_affine=1, weights_bf16=0, wide=False,
              split=False, rays=None, finalize_form=0):
     """Run prep + main + finalize on the simulator. Returns dict like oracle.training_step.
@@ -102,9 +117,15 @@ def sim_step(case_or_fc, B=None, scale=None, batch=None, G=None, bwd=True, adam=
     H = fc[2].shape[-1]
     if G is None:
         G = max(1, (32 if wide in (True, 1) else 64 if wide in (3, 4) else 128) // S)
-    lib().vmsim_set_split(int(split))      # 0 exact fp32 (step_main_h32), 1 step_main_s32, 2 step_main_s32 with the six-product backward
     lib().vmsim_set_finalize_form(int(finalize_form))   # step_finalize_ws: 0 a thread per quad and row group, 1 one thread per quad (the library's choice for many blocks / few rows)
-    lib().vmsim_set_wide(int(wide))       # 0 general kernel, 1 / True step_main_wide<4>, 3 step_main_ws, 4 step_main_wp (hidden 64 / 128)
+    # the kernel family (vl::Family, csrc/step_plan.h).  hidden 32 by split: 0 exact fp32 (step_main_h32), 1 step_main_s32, 2 step_main_s32
+    # with the six-product backward; other widths by wide: 1 / True step_main_wide<4>, 3 step_main_ws (hidden 64 / 128 / 256), 4
+    # step_main_wp (hidden 64 / 128), anything else - and a width the asked-for kernel does not have - the general kernel
+    if H == 32:
+        family = FAMILIES.index(("h32", "s32", "s32_bwd6")[int(split)])
+    else:
+        family = FAMILIES.index("wide" if int(wide) == 1 else "ws" if int(wide) == 3 and H in (64, 128, 256) else
+                                "wp" if int(wide) == 4 and H in (64, 128) else "gen")
     fc_c = [np.ascontiguousarray(a, dtype=np.float32) for a in fc]
     sizes = [a[0].size for a in fc_c]
     P = sum(sizes) + 63
@@ -137,7 +158,7 @@ def sim_step(case_or_fc, B=None, scale=None, batch=None, G=None, bwd=True, adam=
         pcs = np.full_like(pcs, np.nan)              # must not be read
     try:
         rc = lib().vmsim_step(
-        n, R, S, H, G, int(NW), int(xcd_affine), int(weights_bf16), arr, _p(Bc), _p(sc), _p(pcs), _p(z), _p(gd), _p(rgb),
+        n, R, S, H, family, G, int(NW), int(xcd_affine), int(weights_bf16), arr, _p(Bc), _p(sc), _p(pcs), _p(z), _p(gd), _p(rgb),
         _p(sem, ctypes.c_uint8), _p(dm, ctypes.c_uint8), ctypes.c_float(5.0), ctypes.c_float(10.0),
         _p(grads), _p(loss), _p(dD), _p(dC), _p(dO), _p(dV), _p(flags, ctypes.c_int), int(bool(bwd)),
         do_adam, _p(p_out), _p(m), _p(v), int(step), ctypes.c_float(lr), ctypes.c_float(wd))
