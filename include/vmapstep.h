@@ -474,6 +474,60 @@ int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vma
                          float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- frame ingest: a decoded frame into a FrameStore slot, with the table of its objects and their 2-D boxes ----------------------
+ * What the reference's loader does on the host per frame (dataset.py:87-133 + utils.py:36-84 + image_transforms.py:13-33), one
+ * full-frame pass per instance there, four launches here.  Inputs as the image files hold them, row-major [height][width], DEVICE
+ * pointers: rgb uint8 [H][W][3]; depth uint16 or float32 (cfg.depth_f32); inst and sem uint16 or int32, both the same type
+ * (cfg.label_i32).  inst NULL = no labels (the reference's imap_mode): every pixel is id 0, out_inst is all zeros and the table holds
+ * id 0 alone (sem must be NULL too).  sem NULL = class 0 everywhere.  Outputs in store layout [width][height]: out_rgbx uint8 x 4
+ * (r, g, b, 0; 4-byte aligned), out_depth float32, out_inst int32.
+ *
+ * The contract, in [W, H] terms (u = column index, v = row index).  For every id present in inst: count = its pixels, u0 = min u,
+ * u1 = max u + 1, v0, v1 likewise, class_min / class_max over sem on its pixels.  Status, first match:
+ *   VMAPSTEP_INGEST_MIXED        class_min != class_max (the reference raises there, dataset.py:107)
+ *   VMAPSTEP_INGEST_BACKGROUND   the class is one of background_classes[0 .. n_background)
+ *   VMAPSTEP_INGEST_SMALL        u1 - u0 <= min_box or v1 - v0 <= min_box (dataset.py:119; min_box < 0 switches the test off)
+ *   VMAPSTEP_INGEST_ZERO_MARGIN  margin_u or margin_v is 0, margin = trunc(float32(0.5 * bbox_scale) * float32(extent)) - enlarge_bbox
+ *                                on the 0-dim int64 tensors the reference passes it, which torch computes in float32; the reference's
+ *                                ScanNet path sets such an instance to background (dataset.py:269-271), and that is the rule
+ *   VMAPSTEP_INGEST_KEPT         box = clip(u0 - margin_u, 0, W-1), clip(u1 + margin_u, 0, W-1), clip(v0 - margin_v, 0, H-1),
+ *                                clip(v1 + margin_v, 0, H-1): the order u low, u high, v low, v high of vmapstep_sample_object::bbox
+ * out_inst = id where the id is KEPT, else 0.  out_depth = float32(raw) * depth_scale, 0 where that exceeds max_depth.  Id 0 is always
+ * in the table, with the full-frame box (0, W, 0, H) whatever its status (VMAPSTEP_INGEST_ABSENT when no pixel carries it); every
+ * other id that is not KEPT has the box (0, 0, 0, 0).
+ * Ids lie in [-1, max_ids - 2] (table row = id + 1; -1, ScanNet's "unsure" label, is an ordinary row); pixels with any other id are
+ * counted in `overflow` and relabelled 0.  rows_out (DEVICE int32 [2 + max_ids * 8]) receives n_rows, overflow, then n_rows rows of
+ * (id, status, count, box[4], class) in ascending id - np.unique's order.  All combining is integer (sum, minimum, maximum): the
+ * output is bit-identical from call to call.
+ * With background_classes empty, min_box = -1 and sem = NULL the same call does the second half of the reference's ScanNet loader
+ * (dataset.py:266-274) on an already filtered label image - provided cv2.boundingRect over all external contours equals the mask's
+ * min / max extents plus one, which this project could not check against OpenCV itself.
+ *
+ * Everything is enqueued on `stream` (ingest_init, ingest_stats, ingest_decide, ingest_write), nothing waits.  Refused before
+ * anything is enqueued: null or inconsistent arguments (VMAPSTEP_ERR_ARGUMENT); width or height above 4095 (the sampler's limit),
+ * max_ids outside [2, 65537], more than 64 classes (VMAPSTEP_ERR_UNSUPPORTED); a workspace that is not 256-byte aligned or smaller
+ * than vmapstep_ingest_workspace_bytes(max_ids) (VMAPSTEP_ERR_WORKSPACE). */
+#define VMAPSTEP_INGEST_MAX_CLASSES 64
+#define VMAPSTEP_INGEST_ABSENT 0
+#define VMAPSTEP_INGEST_KEPT 1
+#define VMAPSTEP_INGEST_BACKGROUND 2
+#define VMAPSTEP_INGEST_SMALL 3
+#define VMAPSTEP_INGEST_ZERO_MARGIN 4
+#define VMAPSTEP_INGEST_MIXED 5
+typedef struct vmapstep_ingest_cfg {
+    int32_t width, height;
+    int32_t depth_f32;             /* depth: 0 = uint16, 1 = float32 */
+    int32_t label_i32;             /* inst and sem: 0 = uint16, 1 = int32 */
+    float depth_scale, max_depth, bbox_scale;
+    int32_t min_box, max_ids, n_background;
+    int32_t background_classes[VMAPSTEP_INGEST_MAX_CLASSES];
+} vmapstep_ingest_cfg;
+
+int vmapstep_ingest_workspace_bytes(int32_t max_ids, size_t* bytes);
+int vmapstep_ingest_frame(const vmapstep_ingest_cfg* cfg, const void* rgb, const void* depth, const void* inst, const void* sem,
+                          void* out_rgbx, float* out_depth, int32_t* out_inst, int32_t* rows_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -104,6 +104,19 @@ class ViewCfg(ctypes.Structure):
 
 VIEW_MAX_HITS = 16
 
+
+class IngestCfg(ctypes.Structure):
+    """vmapstep_ingest_cfg: the frame shape, the input types and the labelling rules of one vmapstep_ingest_frame call."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("depth_f32", ctypes.c_int32), ("label_i32", ctypes.c_int32),
+                ("depth_scale", ctypes.c_float), ("max_depth", ctypes.c_float), ("bbox_scale", ctypes.c_float),
+                ("min_box", ctypes.c_int32), ("max_ids", ctypes.c_int32), ("n_background", ctypes.c_int32),
+                ("background_classes", ctypes.c_int32 * 64)]
+
+
+INGEST_MAX_CLASSES = 64
+INGEST_ROW_INTS = 8                        # id, status, count, box[4], class
+INGEST_ABSENT, INGEST_KEPT, INGEST_BACKGROUND, INGEST_SMALL, INGEST_ZERO_MARGIN, INGEST_MIXED = range(6)
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -116,6 +129,7 @@ EXPORTS = (
     "vmapstep_clip_box_workspace_bytes", "vmapstep_clip_box_count", "vmapstep_clip_box_emit",
     "vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
     "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
+    "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame",
 )
 
 _libs = {}
@@ -228,8 +242,13 @@ def load(path=None):
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_ingest_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_ingest_frame.argtypes = [ctypes.POINTER(IngestCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
-               "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render"):
+               "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
+               "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_describe_plan", "vmapstep_param_layout", "vmapstep_workspace_bytes", "vmapstep_fwd_bwd", "vmapstep_render",
                "vmapstep_train_steps", "vmapstep_profile_main_kernel",

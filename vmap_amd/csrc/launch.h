@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "view_args.h"
 
 namespace vk { struct WsArgs; }
+struct vmapstep_ingest_cfg;
 
 namespace vl {
 
@@ -104,5 +105,10 @@ int cloud_moments(const float* points, const long long* po, int n_obj, const flo
 int view_count(const vv::ViewArgs& a, hipStream_t st);                           // view_count, view_scan -> a.offsets
 int view_emit(const vv::ViewArgs& a, hipStream_t st);                            // view_emit, view_plan (a.plan_per from view_plan_host)
 int view_composite(const vv::ViewArgs& a, hipStream_t st);
+
+// k_ingest.hip: frame ingest (ingest_kernels.h): ingest_init, ingest_stats, ingest_decide, ingest_write on `st`, nothing between them.
+// The workspace is vl::ingest_layout's; rows_out holds 2 + max_ids * 8 int32.  inst / sem may be null (no labels / class 0 everywhere).
+int ingest_frame(const vmapstep_ingest_cfg& cfg, const void* rgb, const void* depth, const void* inst, const void* sem, void* out_rgbx,
+                 float* out_depth, int* out_inst, int* rows_out, void* workspace, hipStream_t st);
 
 }  // namespace vl

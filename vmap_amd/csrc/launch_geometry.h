@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds and view families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view and ingest families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -39,6 +39,21 @@ constexpr int kViewMaxSamples = 64;
 constexpr int kViewChunk = 128;            // points per chunk of field_query_seg_s32 (four waves x 32-point tiles)
 constexpr int kViewImgBytes = 81920;       // one object's split image (vk::Img32s::BYTES; asserted where both are visible)
 }  // namespace vv
+
+namespace vi {
+constexpr int kIngestWG = 256;             // ingest_init, ingest_stats, ingest_write
+constexpr int kStatsPer = 8;               // consecutive rounds of kIngestWG pixels per ingest_stats workgroup
+constexpr int kStatsPix = kIngestWG * kStatsPer;
+constexpr int kSlots = 64;                 // ids the LDS table of one ingest_stats workgroup holds (a power of two)
+constexpr int kProbes = 4;                 // slots an id tries before it goes to the global table directly
+constexpr int kTableInts = 8;              // a row of the global table: count, u min, u max, v min, v max, class min, class max, unused
+constexpr int kReplicas = 8;               // copies of the global table (workgroup b adds to copy b % kReplicas; ingest_decide merges them)
+constexpr int kReplicaIds = 4096;          // ... while max_ids <= this (1 MiB of tables); one copy beyond
+constexpr int kDecideWG = 1024;            // the single workgroup of ingest_decide
+constexpr int kTile = 64;                  // ingest_write transposes kTile x kTile pixels per workgroup
+constexpr int kMaxIds = 65537;             // every uint16 label and -1
+constexpr int kMaxSide = 4095;             // the sampler's own limit on width and height
+}  // namespace vi
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -162,5 +177,22 @@ inline ViewPlan view_plan_host(const long long* offsets, int n_obj, int samples)
     for (int k = 0; k < n_obj; ++k) p.entries += ceil_div(ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk), p.per);
     return p;
 }
+
+// Frame ingest.  The workspace: the overflow word (pixels whose id has no table row), the statistics of every id
+// (int32 [replicas][max_ids][vi::kTableInts], row = id + 1) and the status of every id (int32 [max_ids]) that ingest_write relabels
+// by.  The table is kept in several copies so that the workgroups' atomics on the rows of the large instances (the wall, the floor:
+// every workgroup meets them) spread over several addresses; the result does not depend on the number of copies.
+inline int ingest_replicas(int max_ids) { return max_ids <= vi::kReplicaIds ? vi::kReplicas : 1; }
+struct IngestLayout {
+    size_t off_table, off_status, bytes;
+};
+inline IngestLayout ingest_layout(int max_ids) {
+    IngestLayout l;
+    l.off_table = 256;
+    l.off_status = l.off_table + ws_up((size_t)ingest_replicas(max_ids) * max_ids * vi::kTableInts * sizeof(int));
+    l.bytes = l.off_status + ws_up((size_t)max_ids * sizeof(int));
+    return l;
+}
+inline int ingest_stats_blocks(int width, int height) { return (int)ceil_div((long long)width * height, vi::kStatsPix); }
 
 }  // namespace vl

@@ -886,6 +886,44 @@ int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vma
     return vl::view_composite(a, st);
 }
 
+// ---- frame ingest ------------------------------------------------------------------------------------------------------------------
+static int check_ingest_ids(int32_t max_ids) {
+    if (max_ids < 2 || max_ids > vi::kMaxIds)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "ingest limits: 2 <= max_ids <= %d (max_ids=%d)", vi::kMaxIds, max_ids);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_ingest_workspace_bytes(int32_t max_ids, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_ingest_ids(max_ids)) return rc;
+    *bytes = vl::ingest_layout(max_ids).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_ingest_frame(const vmapstep_ingest_cfg* cfg, const void* rgb, const void* depth, const void* inst, const void* sem,
+                          void* out_rgbx, float* out_depth, int32_t* out_inst, int32_t* rows_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: cfg is null");
+    if (!rgb || !depth || !out_rgbx || !out_depth || !out_inst || !rows_out) return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: null argument");
+    if (sem && !inst) return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: sem without inst");
+    if (cfg->width < 1 || cfg->height < 1 || cfg->n_background < 0 || (cfg->depth_f32 | cfg->label_i32) & ~1)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: width=%d height=%d n_background=%d depth_f32=%d label_i32=%d", cfg->width, cfg->height,
+                    cfg->n_background, cfg->depth_f32, cfg->label_i32);
+    if (!(cfg->bbox_scale >= 0.0f) || !std::isfinite(cfg->bbox_scale) || !std::isfinite(cfg->depth_scale) || std::isnan(cfg->max_depth))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: bbox_scale must be finite and >= 0, depth_scale finite, max_depth a number");
+    if (reinterpret_cast<uintptr_t>(out_rgbx) % 4) return fail(VMAPSTEP_ERR_ARGUMENT, "ingest: out_rgbx must be 4-byte aligned");
+    if (cfg->width > vi::kMaxSide || cfg->height > vi::kMaxSide || cfg->n_background > VMAPSTEP_INGEST_MAX_CLASSES)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "ingest limits: width, height <= %d, n_background <= %d (width=%d height=%d n_background=%d)",
+                    vi::kMaxSide, VMAPSTEP_INGEST_MAX_CLASSES, cfg->width, cfg->height, cfg->n_background);
+    if (int rc = check_ingest_ids(cfg->max_ids)) return rc;
+    const size_t need = vl::ingest_layout(cfg->max_ids).bytes;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "ingest workspace must be 256-byte aligned and >= %zu bytes", need);
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::ingest_frame(*cfg, rgb, depth, inst, sem, out_rgbx, out_depth, reinterpret_cast<int*>(out_inst), reinterpret_cast<int*>(rows_out),
+                            workspace, static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

@@ -20,7 +20,7 @@ so the batched sampler reads the shared store directly: ``FrameSampler.set_objec
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -43,17 +43,23 @@ class FrameStore:
     def put(self, rgb: torch.Tensor, depth: torch.Tensor, inst: torch.Tensor, t_wc: torch.Tensor, frame_id: int) -> int:
         """Store one frame (rgb u8 [W,H,3], depth f32 [W,H], inst int [W,H], t_wc [4,4]) in a free slot; returns the
         slot with a reference count of 0 - objects that keep the frame ``retain`` it, ``collect()`` frees the rest."""
+        slot = self.free_slot()
+        self.rgbx[slot, :, :, :3] = rgb.to(self.device)
+        self.depth[slot] = depth.to(self.device)
+        self.inst[slot] = inst.to(self.device, torch.int32)
+        self.t_wc[slot] = t_wc.to(self.device)
+        self.frame_of_slot[slot] = int(frame_id)
+        return slot
+
+    def free_slot(self) -> int:
+        """The slot the next frame goes to (``put`` and ``ingest.FrameIngest.put``): the first one that no object references and no
+        frame waits in for its ``retain``."""
         try:
             slot = self.refs.index(0, 0)
             while self.frame_of_slot[slot] is not None:          # occupied by a frame nobody retained yet
                 slot = self.refs.index(0, slot + 1)
         except ValueError:
             raise RuntimeError("FrameStore is full: raise capacity or collect() unreferenced frames") from None
-        self.rgbx[slot, :, :, :3] = rgb.to(self.device)
-        self.depth[slot] = depth.to(self.device)
-        self.inst[slot] = inst.to(self.device, torch.int32)
-        self.t_wc[slot] = t_wc.to(self.device)
-        self.frame_of_slot[slot] = int(frame_id)
         return slot
 
     def retain(self, slot: int):
