@@ -74,6 +74,8 @@ typedef struct vmapstep_tuning {
                                    /* always three-tile rounds (hidden 128), bit 2 = never three-tile rounds (A/B) */
                                    /* step_main_s32 (hidden 32), measurement build only: bit 3 = the B_layer.weight   */
                                    /* gradient summed with one butterfly per value (A/B: same bits either way)        */
+                                   /* bit 4 = the former order of its global loads: B_layer.weight behind the image   */
+                                   /* copy, switches / normalisers and z where they are used (A/B: same bits)          */
 } vmapstep_tuning;
 
 typedef struct vmapstep_shape {

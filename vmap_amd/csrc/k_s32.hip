@@ -6,9 +6,9 @@
 namespace vl {
 
 namespace {
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false>
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false>
 int main_v(const vk::StepArgs& a, hipStream_t st) {
-    auto kern = vk::step_main_s32<BWD, MULTI, STAMPS, W3, B6, PV>;
+    auto kern = vk::step_main_s32<BWD, MULTI, STAMPS, W3, B6, PV, OL>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), vk::Img32s::LDS_BYTES, "step_main_s32")) return rc;
     const int grid = a.xcd_affine ? 8 * ((a.n_obj + 7) / 8) * a.NW : a.n_obj * a.NW;
     VL_LAUNCH_MAIN(kern, dim3(grid), dim3(vk::kWG), vk::Img32s::LDS_BYTES, st, a);
@@ -17,6 +17,17 @@ int main_v(const vk::StepArgs& a, hipStream_t st) {
 template <bool BWD, bool STAMPS>
 int main_bs(const vk::StepArgs& a, hipStream_t st) {
     const bool multi = a.NW < a.NG;
+#ifdef VMAPSTEP_AB
+    if (a.ab_flags & 2) {                    // tuning.ws_flags bit 4: the former order of the global loads (training instantiations, three-product backward)
+        if constexpr (BWD && !STAMPS) {
+            if (!a.bwd6 && !(a.ab_flags & 1)) {
+                if (a.weights_bf16) return multi ? main_v<true, true, false, false, false, false, true>(a, st) : main_v<true, false, false, false, false, false, true>(a, st);
+                return multi ? main_v<true, true, false, true, false, false, true>(a, st) : main_v<true, false, false, true, false, false, true>(a, st);
+            }
+        }
+        return fail(-2, "tuning.ws_flags bit 4 (the former load order of step_main_s32): training steps without phase stamps, bit 3 or the six-product backward");
+    }
+#endif
     if (a.weights_bf16) return multi ? main_v<BWD, true, STAMPS, false>(a, st) : main_v<BWD, false, STAMPS, false>(a, st);
     if constexpr (BWD && !STAMPS) {          // the six-product backward (tuning.kernel = VMAPSTEP_KERNEL_S32_BWD6): training instantiations only
         if (a.bwd6) return multi ? main_v<true, true, false, true, true>(a, st) : main_v<true, false, false, true, true>(a, st);

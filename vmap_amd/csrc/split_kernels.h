@@ -805,9 +805,12 @@ __device__ __forceinline__ void stage_get_s(float (&q)[4], const float* stage, i
 // step_main_s32<BWD, MULTI, STAMPS, W3>:  W3 = float32 weights as three planes (false: bf16 weights, one plane)
 // ---------------------------------------------------------------------------------------------------------
 // PV (measurement build only): the B_layer.weight gradient with one butterfly per value, the form before wave_reduce.h
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false>
+// OL (measurement build only, tuning.ws_flags bit 4): the former order of the global loads, word for word - B_layer.weight read
+// behind the image copy, the per-object switches / normalisers and the sample's z loaded where they are used
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false>
 __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     static_assert(!B6 || (W3 && BWD), "six-product backward: float32 weights, training instantiations");
+    constexpr int OLD = OL ? 7 : VS_LOADS_OLD;     // bit 0: B_layer, bit 1: switches / normalisers, bit 2: z
     using I = Img32s;
     using F = Flat32;
     constexpr int H = 32;
@@ -869,10 +872,32 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     const int lray = valid ? pt / a.S : 0;
     const int smp = valid ? pt - lray * a.S : 0;
     const int ray = ray0 + lray;
+    // B_layer.weight rows of this lane's directions: hi = 0 -> 0..10, hi = 1 -> 11..20 (+ one dummy).  Requested in front of the
+    // sample point (whose loads the rays form of load_point waits for on the spot) and WAITED FOR, with the point, in front of the
+    // image copy (opaque() is the use that places the wait, the fence keeps it there): vmcnt retires in issue order and the
+    // compiler flushes it to zero at any wait while an LDS-DMA is pending, so behind the copy the wait for these values is a wait
+    // for all 76 KiB of the image.
+    float Bv[11][3];
+    if constexpr (!(OLD & 1)) {
+#pragma unroll
+        for (int i = 0; i < 11; ++i) {
+            const float* bp = Bg + 3 * (hi ? (i < 10 ? 11 + i : 20) : i);
+            Bv[i][0] = bp[0]; Bv[i][1] = bp[1]; Bv[i][2] = bp[2];
+        }
+        wv::sched_fence();
+    }
     float px3[3] = {0.0f, 0.0f, 0.0f};
     if (VS_ABL & 512) { px3[0] = 0.01f * (float)lane; px3[1] = 0.02f * (float)wave; px3[2] = 0.003f * (float)(lane + wave); }
     else if (valid) load_point(a, obj, ray, smp, px3[0], px3[1], px3[2]);
-    // ---- asynchronous copy of the parameter image into LDS (issued behind the loads of the sample point, whose latency its 20 instructions cover; lands during the encoding) ----
+    if constexpr (!(OLD & 1)) {
+#pragma unroll
+        for (int i = 0; i < 11; ++i) { Bv[i][0] = wv::opaque(Bv[i][0]); Bv[i][1] = wv::opaque(Bv[i][1]); Bv[i][2] = wv::opaque(Bv[i][2]); }
+        px3[0] = wv::opaque(px3[0]); px3[1] = wv::opaque(px3[1]); px3[2] = wv::opaque(px3[2]);
+        wv::sched_fence();
+    }
+    // ---- asynchronous copy of the parameter image into LDS: issued once the sample point and B_layer.weight have arrived, so the
+    // encoding needs no memory wait and the copy lands under it (the barrier behind the encoding drains it).  (OL: issued behind
+    // the sample point's loads, B_layer.weight read behind it - the encoding starts when the image has landed.) ----
     if (grp == wgo && !(VS_ABL & 256)) {
         const char* src = gimg + wave * 1024 + lane * 16;
 #pragma unroll
@@ -884,9 +909,12 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     float proj[11];
 #pragma unroll
     for (int i = 0; i < 11; ++i) {
+        if constexpr (OLD & 1) {
         const int d0 = i, d1 = i < 10 ? 11 + i : 20;
         const float b0 = hi ? Bg[3 * d1] : Bg[3 * d0], b1 = hi ? Bg[3 * d1 + 1] : Bg[3 * d0 + 1], b2 = hi ? Bg[3 * d1 + 2] : Bg[3 * d0 + 2];
         proj[i] = fmaf(t[2], b2, fmaf(t[1], b1, t[0] * b0));          // embedding.py:84 B_layer(tensor)
+        } else
+        proj[i] = fmaf(t[2], Bv[i][2], fmaf(t[1], Bv[i][1], t[0] * Bv[i][0]));
     }
 
     VS_MARK(1);
@@ -924,11 +952,16 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     split_planes<24, 3>(e2, e2h, e2m, e2l);
     VS_MARK(2);
     __syncthreads();        // parameter image landed (the barrier drains the LDS-DMA), composite buffer zeroed
-    // ground truth of the ray this lane composites: its six vector loads fly during the MLP forward (at the compositing they
-    // cost a full memory round trip of an otherwise idle workgroup)
+    // ground truth of the ray this lane composites, the per-object switches and normalisers (two 16-byte loads) and this lane's z:
+    // independent vector loads that fly during the MLP forward and are waited for once (at the compositing each would cost a full
+    // memory round trip of an otherwise idle workgroup; OL: the per-object part and z are loaded there)
     RayMeta rays_meta;
+    float zv = 0.0f;                                 // 0 for padding lanes
     if (VS_ABL & 1024) { rays_meta.sem = 1; rays_meta.dm = 1; rays_meta.gtd = 1.5f; rays_meta.q0 = 0.2f; rays_meta.q1 = 0.3f; rays_meta.q2 = 0.4f; rays_meta.inv_dd = rays_meta.inv_o = rays_meta.inv_s = 0.01f; }
     else rays_meta = load_ray_meta_rays(a, obj, ray0 + min(4 * wave + (lane >> 4), nrays - 1));
+    ObjMeta obj_meta = {};
+    if constexpr (!(OLD & 2)) { if (!(VS_ABL & 1024)) obj_meta = load_obj_meta(a, obj); }
+    if constexpr (!(OLD & 4)) { if (!(VS_ABL & 512) && valid) zv = a.z[obj * a.z_so + ray * a.z_sr + smp * a.z_ss]; }
     wv::sched_fence();
 
     // ---- field MLP forward (model.py:59-83) ----
@@ -963,6 +996,18 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         relu_to(hc, accC);                                        // :81 color_linear
     }
     VS_MARK(3);
+    // the one wait for the loads requested in front of the forward, and the three divisions, HERE: the loaded values are tied behind
+    // the forward's last output (after(): no instruction), and the volatile tie on the results keeps the divisions from sinking
+    // behind the barrier into the compositing, where the compiler would otherwise place them
+    if constexpr (!(OLD & 4)) zv = wv::after(zv, hc[15]);
+    if constexpr (!(OLD & 2)) {
+        if (!(VS_ABL & 1024)) {
+            obj_meta.st.x = wv::after(obj_meta.st.x, hc[15]); obj_meta.st.y = wv::after(obj_meta.st.y, hc[15]); obj_meta.st.z = wv::after(obj_meta.st.z, hc[15]);
+            rays_meta = finish_ray_meta(obj_meta, rays_meta);
+            rays_meta.inv_dd = wv::after(rays_meta.inv_dd, rays_meta.inv_o); rays_meta.inv_s = wv::after(rays_meta.inv_s, rays_meta.inv_o);
+            rays_meta.inv_o = wv::after(rays_meta.inv_o, rays_meta.inv_s);
+        }
+    }
     {
         float ra = 0.0f, r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
 #pragma unroll
@@ -977,7 +1022,9 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         ra += SM[I::B_A]; r0 += SM[I::B_OC]; r1 += SM[I::B_OC + 1]; r2 += SM[I::B_OC + 2];
         if (valid && hi == 0) {
             float* row = cb + pt * 8;
+            if constexpr (OLD & 4)
             row[6] = (VS_ABL & 512) ? 1.0f + 0.1f * (float)smp : a.z[obj * a.z_so + ray * a.z_sr + smp * a.z_ss];
+            else row[6] = (VS_ABL & 512) ? 1.0f + 0.1f * (float)smp : zv;
             row[0] = sigmoidf_acc(ra * 10.0f);                   // :77 raw*10 ; render_rays.py:6 sigmoid
             row[1] = sigmoidf_acc(r0);                           // :83 sigmoid(raw_color)
             row[2] = sigmoidf_acc(r1);
@@ -994,9 +1041,11 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     VS_MARK(5);
     {
         const StepArgs& al = wv::kernarg_late(a);
+        if constexpr (OLD & 2) {
         if (!(VS_ABL & 2048))
         composite_phase<BWD>(al, cb, loss_cells, obj, ray0, nrays, wave, lane, tid,
                              (VS_ABL & 1024) ? rays_meta : finish_ray_meta(al, obj, rays_meta));
+        } else if (!(VS_ABL & 2048)) composite_phase<BWD>(al, cb, loss_cells, obj, ray0, nrays, wave, lane, tid, rays_meta);
     }
     if (!(VS_ABL & 65536)) __syncthreads();
     VS_MARK(6);
@@ -1317,9 +1366,9 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 #undef VS_MARK
 }
 
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false>
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false>
 __global__ __launch_bounds__(kWG, 1) void step_main_s32(const StepArgs a) {
-    step_main_s32_body<BWD, MULTI, STAMPS, W3, B6, PV>(a);
+    step_main_s32_body<BWD, MULTI, STAMPS, W3, B6, PV, OL>(a);
 }
 
 }  // namespace vk

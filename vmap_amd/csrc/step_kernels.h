@@ -31,6 +31,9 @@
 #ifndef VS_ABL                   /* measurement builds only (split_kernels.h) */
 #define VS_ABL 0
 #endif
+#ifndef VS_LOADS_OLD             /* measurement builds only (tests/tools/build_variant.py): step_main_s32's former load order part by part - */
+#define VS_LOADS_OLD 0           /* bit 0 = B_layer behind the image copy, bit 1 = finish_ray_meta, bit 2 = z where row[6] is written         */
+#endif
 namespace vk {
 
 using wv::f32x16;
@@ -94,6 +97,7 @@ struct StepArgs {
     int PR; int* row_tab;
     int ab_flags;                      // measurement build (-DVMAPSTEP_AB) only, hidden 32: bit 0 = the launcher takes the step_main_s32 instantiation that reduces the
                                        // B_layer.weight gradient with one butterfly per value (tuning.ws_flags bit 3; float32 weights, training); no kernel reads it
+                                       // bit 1 = ... the instantiation with the former order of the global loads (tuning.ws_flags bit 4; training)
 };
 
 // Sample point `smp` of ray `ray` of object `obj` in the object frame: read from the points tensor (train.py:272 batch_input_pcs),
@@ -684,6 +688,26 @@ __device__ __forceinline__ RayMeta finish_ray_meta(const StepArgs& a, int obj, R
     m.inv_dd = a.flags[0] ? 0.0f : 1.0f / (a.stats[obj * 4 + 0] + 1e-10f);            // render_rays.py:68-73,87
     m.inv_o = a.flags[1] ? 0.0f : 1.0f / (a.stats[obj * 4 + 1] + 1e-10f);
     m.inv_s = a.flags[2] ? 0.0f : 1.0f / (a.stats[obj * 4 + 2] + 1e-10f);
+    return m;
+}
+// ... or the per-object part as ONE round trip next to the per-ray loads: flags[0..3] and stats[obj*4 .. +3] as two 16-byte loads
+// (the workspace keeps both vectors 16-byte aligned: step_plan.h), and, once they have arrived, the normalisers as selects of the
+// same expressions in the same order as finish_ray_meta.  finish_ray_meta's form is three dependent pairs flag -> branch -> stat,
+// six round trips in a row.
+struct alignas(16) MetaI4 { int x, y, z, w; };
+struct alignas(16) MetaF4 { float x, y, z, w; };
+struct ObjMeta { MetaI4 fl; MetaF4 st; };
+__device__ __forceinline__ ObjMeta load_obj_meta(const StepArgs& a, int obj) {
+    ObjMeta o;
+    o.fl = *reinterpret_cast<const MetaI4*>(a.flags);
+    o.st = *reinterpret_cast<const MetaF4*>(a.stats + obj * 4);
+    return o;
+}
+__device__ __forceinline__ RayMeta finish_ray_meta(const ObjMeta& o, RayMeta m) {
+    const float dd = 1.0f / (o.st.x + 1e-10f), io = 1.0f / (o.st.y + 1e-10f), is = 1.0f / (o.st.z + 1e-10f);
+    m.inv_dd = o.fl.x ? 0.0f : dd;                                                     // render_rays.py:68-73,87
+    m.inv_o = o.fl.y ? 0.0f : io;
+    m.inv_s = o.fl.z ? 0.0f : is;
     return m;
 }
 __device__ __forceinline__ RayMeta load_ray_meta(const StepArgs& a, int obj, int rr) {
