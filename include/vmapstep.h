@@ -476,6 +476,47 @@ int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vma
                          float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scene view (an addition to ABI v7): a view of 1 <= n_groups <= VMAPSTEP_VIEW_MAX_GROUPS FIELD GROUPS, all composited into one image.
+ * Group g carries hidden_g in {32, 64, ..., 256}, n_obj_g >= 1 fields with float32 weights (`params` + `pe_scale`, stacked as for the
+ * step) and samples_g in [1, 64] samples per hit.  The objects are numbered through the groups in order; `boxes`, `centers`, `offsets`
+ * and `instance` use that global index k, and the total object count is <= 256.  The object stack (hidden 32) plus the background
+ * model (hidden 128, a room box, more samples) is the two-group case; one field of hidden 256 is the one-group case.
+ *
+ * The contract is the one above, word for word, with `samples` replaced by the samples_g of the object's group: dt = (t_far - t_near)
+ * / samples_g, t_s = fma(s + 0.5f, dt, t_near) for s < samples_g.  The field gives occupancy sigmoid(10 * raw) and colour exactly as
+ * vmapstep_query_points does at hidden_g.  The composite is unchanged: all samples of all boxes a pixel hits in ascending (t, k) with
+ * the same accumulation order (the entries of one pixel may have different sample counts), the VMAPSTEP_VIEW_MAX_HITS cap by
+ * (t_near, k), instance = the global index with the largest own weight.
+ * Buffers: `pairs` ordered by (k, pixel), 16 bytes each, as above.  `sample_occ` / `sample_rgb` hold samples_g values (x 3) per pair
+ * of group g, laid out group after group and inside a group pair after pair: n_samples = sum_g pairs_g * samples_g values.
+ * Bit-identical from call to call and for any split of the pixel range into calls; and a group's pair records and sample values do
+ * not depend on which other groups are in the scene (its section of the buffers holds the bits a scene of that group alone writes).
+ *
+ * The protocol is the one above: vmapstep_scene_view_count -> one host read of the offsets [n_obj + 1] -> vmapstep_scene_view_render
+ * with the same cfg, groups, boxes and workspace.  cfg->samples and cfg->n_obj are NOT read by these entry points (the groups say
+ * both).  `params` and `pe_scale` of a group are read by vmapstep_scene_view_render only and may be NULL in the other two.
+ * Limits, refused with VMAPSTEP_ERR_UNSUPPORTED before anything touches a device: 1 <= n_groups <= 4, hidden a multiple of 32 in
+ * [32, 256], 1 <= samples <= 64, n_obj_g >= 1, 1 <= sum n_obj_g <= 256, 1 <= width, height <= 16384, n_samples < 2^31.
+ * Workspace: 256-byte aligned, >= vmapstep_scene_view_workspace_bytes (VMAPSTEP_ERR_WORKSPACE otherwise) = with up(x) = x rounded
+ * up to 256:  sum_g up(n_obj_g * image_g) + up(8 * sum n_obj_g * ceil((pix_end - pix_begin) / 64)) + up(16 * (4 * 2048 + 256)),
+ * image_g = 81920 bytes at hidden 32 (the split image) and 4 * roundup(4 H^2 + 253 H + 72, 1024) bytes at the other widths (the
+ * float32 image vmapstep_query_points packs). */
+#define VMAPSTEP_VIEW_MAX_GROUPS 4
+typedef struct vmapstep_view_group {
+    int32_t hidden, n_obj, samples, reserved;    /* reserved: 0 */
+    const vmapstep_params* params;               /* the group's stacked fields */
+    const vmapstep_tensor* pe_scale;
+} vmapstep_view_group;
+
+int vmapstep_scene_view_workspace_bytes(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, size_t* bytes);
+int vmapstep_scene_view_count(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, const float* boxes,
+                              int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_scene_view_render(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups,
+                               const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                               void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                               float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- frame ingest: a decoded frame into a FrameStore slot, with the table of its objects and their 2-D boxes ----------------------
  * What the reference's loader does on the host per frame (dataset.py:87-133 + utils.py:36-84 + image_transforms.py:13-33), one
  * full-frame pass per instance there, four launches here.  Inputs as the image files hold them, row-major [height][width], DEVICE

@@ -103,6 +103,13 @@ class ViewCfg(ctypes.Structure):
 
 
 VIEW_MAX_HITS = 16
+VIEW_MAX_GROUPS = 4
+
+
+class ViewGroup(ctypes.Structure):
+    """vmapstep_view_group: one field group of a scene view (its hidden width, object count, samples per hit and stacked fields)."""
+    _fields_ = [("hidden", ctypes.c_int32), ("n_obj", ctypes.c_int32), ("samples", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("params", ctypes.POINTER(Params)), ("pe_scale", ctypes.POINTER(Tensor))]
 
 
 class IngestCfg(ctypes.Structure):
@@ -129,6 +136,7 @@ EXPORTS = (
     "vmapstep_clip_box_workspace_bytes", "vmapstep_clip_box_count", "vmapstep_clip_box_emit",
     "vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
     "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
+    "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",
     "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame",
 )
 
@@ -242,12 +250,20 @@ def load(path=None):
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _scene = [ctypes.POINTER(ViewCfg), ctypes.POINTER(ViewGroup), ctypes.c_int32]
+    lib.vmapstep_scene_view_workspace_bytes.argtypes = _scene + [ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_scene_view_count.argtypes = _scene + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_scene_view_render.argtypes = _scene + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.vmapstep_ingest_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
     lib.vmapstep_ingest_frame.argtypes = [ctypes.POINTER(IngestCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
                "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
+               "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",
                "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_describe_plan", "vmapstep_param_layout", "vmapstep_workspace_bytes", "vmapstep_fwd_bwd", "vmapstep_render",

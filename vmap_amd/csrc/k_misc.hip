@@ -1,5 +1,5 @@
 // k_misc.hip - the kernels either side of the step: the inference query (query_kernels.h), its segmented
-// form for view rendering (field_query_seg_s32) and the
+// forms for view rendering (field_query_seg_s32, field_query_seg_gen) and the
 // batched frame sampler (sample_kernels.h; row 1).  gfx950 only.
 #include "launch.h"
 #include "query_split_kernels.h"
@@ -48,6 +48,33 @@ int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entrie
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(vk::field_query_seg_s32<>), vk::kQuerySplitLds, "field_query_seg_s32")) return rc;
     hipLaunchKernelGGL(vk::field_query_seg_s32<>, dim3((unsigned)entries), dim3(vk::kWG), vk::kQuerySplitLds, st, a);
     return launched("field_query_seg_s32");
+}
+
+template <int NB>
+static int launch_seg_gen(const vv::ViewArgs& a, unsigned entries, hipStream_t st) {
+    const size_t lds = NB > 4 ? (size_t)NB * 1024 * vk::kWaves * sizeof(float) : 0;               // second activation set (NB > 4)
+    if (NB > 4)
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(vk::field_query_seg_gen<NB>), lds, "field_query_seg_gen")) return rc;
+    hipLaunchKernelGGL(vk::field_query_seg_gen<NB>, dim3(entries), dim3(vk::kWG), lds, st, a);
+    return launched("field_query_seg_gen");
+}
+
+int scene_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st) {
+    if (pack.hidden == 32) return view_field(pack, a, entries, st);
+    // every object's float32 image (step_prep's pack role, zero mask-statistics blocks), then one workgroup per plan entry
+    hipLaunchKernelGGL(vk::step_prep<>, dim3(a.n_obj * (vk::gen_layout(pack.hidden).imgp / 1024)), dim3(vk::kWG), 3 * vk::kWG * sizeof(int), st, pack);
+    if (int rc = launched("step_prep")) return rc;
+    if (entries <= 0) return 0;
+    switch (pack.hidden / 32) {
+        case 2: return launch_seg_gen<2>(a, (unsigned)entries, st);
+        case 3: return launch_seg_gen<3>(a, (unsigned)entries, st);
+        case 4: return launch_seg_gen<4>(a, (unsigned)entries, st);
+        case 5: return launch_seg_gen<5>(a, (unsigned)entries, st);
+        case 6: return launch_seg_gen<6>(a, (unsigned)entries, st);
+        case 7: return launch_seg_gen<7>(a, (unsigned)entries, st);
+        case 8: return launch_seg_gen<8>(a, (unsigned)entries, st);
+    }
+    return fail(-2, "scene view: no field kernel for hidden=%d", pack.hidden);
 }
 
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st) {

@@ -38,6 +38,7 @@ constexpr int kViewMaxHits = 16;           // VMAPSTEP_VIEW_MAX_HITS
 constexpr int kViewMaxSamples = 64;
 constexpr int kViewChunk = 128;            // points per chunk of field_query_seg_s32 (four waves x 32-point tiles)
 constexpr int kViewImgBytes = 81920;       // one object's split image (vk::Img32s::BYTES; asserted where both are visible)
+constexpr int kViewMaxGroups = 4;          // VMAPSTEP_VIEW_MAX_GROUPS: field groups of a scene view
 }  // namespace vv
 
 namespace vi {
@@ -167,14 +168,75 @@ inline ViewLayout view_layout(int n_obj, long long pix_begin, long long pix_end)
 struct ViewPlan {
     long long per, entries;
 };
-inline ViewPlan view_plan_host(const long long* offsets, int n_obj, int samples) {
+inline ViewPlan view_plan_host_target(const long long* offsets, int n_obj, int samples, long long target) {
     long long chunks = 0;
     for (int k = 0; k < n_obj; ++k) chunks += ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk);
     ViewPlan p;
-    p.per = ceil_div(chunks, kViewWgTarget);
+    p.per = ceil_div(chunks, target);
     p.per = p.per < 1 ? 1 : p.per;
     p.entries = 0;
     for (int k = 0; k < n_obj; ++k) p.entries += ceil_div(ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk), p.per);
+    return p;
+}
+inline ViewPlan view_plan_host(const long long* offsets, int n_obj, int samples) {
+    return view_plan_host_target(offsets, n_obj, samples, kViewWgTarget);
+}
+
+// Scene view: up to vv::kViewMaxGroups field groups, each with its own hidden width and samples per hit, composited into one image.
+// Objects are numbered through the groups in order.  The workspace: group after group the parameter images of its objects in the
+// layout its field kernel reads (hidden 32: vv::kViewImgBytes split images; wider: view_wide_image_floats float32 images, what
+// vk::gen_layout(hidden).imgp is - asserted in query_kernels.h), then the block totals and the launch plan as in ViewLayout.
+struct SceneGroup {
+    int hidden, n_obj, samples;
+};
+constexpr long long view_wide_image_floats(int H) { return (4ll * H * H + 253ll * H + 72 + 1023) / 1024 * 1024; }
+inline size_t view_group_image_bytes(int hidden) {
+    return hidden == 32 ? (size_t)vv::kViewImgBytes : (size_t)view_wide_image_floats(hidden) * sizeof(float);
+}
+// Plan entries per group.  field_query_seg_s32 keeps kViewWgTarget.  field_query_seg_gen is __launch_bounds__(kWG, 1) and from
+// hidden 160 holds NB x 16 KiB of LDS: ONE workgroup is resident per compute unit, so 256 entries would fill the chip exactly once
+// and any excess entry (every object rounds up once) would cost a whole second round.  Eight entries per compute unit (as
+// kNnItemsTarget, kObbBlocksTarget) bound that tail by 1/8 of a compute unit's share; an entry has no set-up to amortise (the
+// weights are streamed from L2, nothing is staged per workgroup).
+constexpr long long kViewWideWgTarget = 2048;
+inline long long view_group_target(int hidden) { return hidden == 32 ? kViewWgTarget : kViewWideWgTarget; }
+constexpr long long kScenePlanCap = vv::kViewMaxGroups * kViewWideWgTarget + vv::kViewMaxObj;   // every object rounds up once
+struct SceneLayout {
+    size_t off_img[vv::kViewMaxGroups], off_blk, off_plan, bytes;
+    int n_obj;                                                              // all groups
+};
+inline SceneLayout scene_layout(const SceneGroup* g, int n_groups, long long pix_begin, long long pix_end) {
+    SceneLayout l{};
+    size_t at = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        l.off_img[i] = at;
+        at += ws_up((size_t)g[i].n_obj * view_group_image_bytes(g[i].hidden));
+        l.n_obj += g[i].n_obj;
+    }
+    l.off_blk = at;
+    l.off_plan = l.off_blk + ws_up((size_t)l.n_obj * view_blocks(pix_begin, pix_end) * sizeof(long long));
+    l.bytes = l.off_plan + ws_up((size_t)kScenePlanCap * 4 * sizeof(int));
+    return l;
+}
+// The launch plan of a scene from the host copy of the pair offsets: view_plan_host's formula per group (its own sample count and
+// workgroup target).  The entries of a group are contiguous: scene_view_plan scans them in object order.  `shift`: the groups'
+// sample sections lie one after the other, inside a group pair after pair, so sample s of pair pr (a global pair index) of group g
+// is element pr * samples_g + shift[g] + s of sample_occ.  `samples`: all groups.
+struct ScenePlan {
+    long long per[vv::kViewMaxGroups], entries[vv::kViewMaxGroups], first[vv::kViewMaxGroups], shift[vv::kViewMaxGroups], samples;
+};
+inline ScenePlan scene_plan_host(const long long* offsets, const SceneGroup* g, int n_groups) {
+    ScenePlan p{};
+    int k0 = 0;
+    long long first = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        const ViewPlan v = view_plan_host_target(offsets + k0, g[i].n_obj, g[i].samples, view_group_target(g[i].hidden));
+        p.per[i] = v.per; p.entries[i] = v.entries; p.first[i] = first;
+        p.shift[i] = p.samples - offsets[k0] * g[i].samples;
+        p.samples += (offsets[k0 + g[i].n_obj] - offsets[k0]) * g[i].samples;
+        first += v.entries;
+        k0 += g[i].n_obj;
+    }
     return p;
 }
 

@@ -1,6 +1,8 @@
 // view_args.h - the argument block of the view kernels (view_kernels.h: view_count, view_scan, view_emit, view_plan, view_composite;
-// query_split_kernels.h: field_query_seg_s32).  Plain C++: the C ABI unit fills it, the two kernel units launch with it.
+// query_split_kernels.h: field_query_seg_s32; query_kernels.h: field_query_seg_gen).  Plain C++: the C ABI unit fills it, the two
+// kernel units launch with it.
 #pragma once
+#include "launch_geometry.h"
 #include "view_geometry.h"
 
 namespace vv {
@@ -22,6 +24,12 @@ struct ViewArgs {
     float* rgb;                            // [cap * samples][3]
     float* depth; float* color; float* opacity; int* instance;      // [width * height] (x 3)
     int* overflow;                         // [1] pixels that hit more than kViewMaxHits boxes (added to)
+    // The scene form (scene_view_count / _emit / _plan / _composite): field groups.  Objects [g_end[g - 1], g_end[g]) belong to group g
+    // (unused groups: n_obj); cam.samples is not read, an object's sample count is its group's; sample s of pair pr of group g is
+    // element pr * g_samples[g] + g_shift[g] + s of occ; a plan entry of group g holds g_per[g] chunks.
+    // The field kernels never read these: each group's launch gets an argument block of its own (vl::scene_field).
+    int g_end[kViewMaxGroups], g_samples[kViewMaxGroups];
+    long long g_shift[kViewMaxGroups], g_per[kViewMaxGroups];
 };
 
 }  // namespace vv

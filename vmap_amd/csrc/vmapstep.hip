@@ -886,6 +886,150 @@ int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vma
     return vl::view_composite(a, st);
 }
 
+// ---- scene view: field groups of their own width and sample count, one image ---------------------------------------------------------
+static_assert(VMAPSTEP_VIEW_MAX_GROUPS == vv::kViewMaxGroups, "one group limit");
+
+// every limit of the scene section, then the arguments the camera shares with the single-group form; fills g[] and the object total
+static int check_scene(const vmapstep_view_cfg* c, const vmapstep_view_group* groups, int32_t n_groups, vl::SceneGroup* g, int* n_obj) {
+    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: cfg is null");
+    if (n_groups < 1 || n_groups > vv::kViewMaxGroups)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: 1 <= n_groups <= %d (n_groups=%d)", vv::kViewMaxGroups, n_groups);
+    if (!groups) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: groups is null");
+    long long total = 0;
+    for (int32_t i = 0; i < n_groups; ++i) {
+        const vmapstep_view_group& q = groups[i];
+        if (q.hidden < 32 || q.hidden > 256 || q.hidden % 32 != 0 || q.samples < 1 || q.samples > vv::kViewMaxSamples || q.n_obj < 1)
+            return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: hidden a multiple of 32 in [32, 256], 1 <= samples <= %d, n_obj >= 1 "
+                        "(group %d: hidden=%d samples=%d n_obj=%d)", vv::kViewMaxSamples, (int)i, q.hidden, q.samples, q.n_obj);
+        g[i] = vl::SceneGroup{q.hidden, q.n_obj, q.samples};
+        total += q.n_obj;
+    }
+    if (total > vv::kViewMaxObj || c->width < 1 || c->height < 1 || c->width > 16384 || c->height > 16384)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: objects of all groups <= %d, 1 <= width, height <= 16384 (objects=%lld width=%d height=%d)",
+                    vv::kViewMaxObj, total, c->width, c->height);
+    if (c->pix_begin < 0 || c->pix_end < c->pix_begin || c->pix_end > (int64_t)c->width * c->height)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: pixel range [%lld, %lld) outside the image", (long long)c->pix_begin, (long long)c->pix_end);
+    if (!(std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy)) || c->fx == 0.0f || c->fy == 0.0f)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: intrinsics must be finite with fx, fy != 0");
+    *n_obj = (int)total;
+    return VMAPSTEP_OK;
+}
+
+static int check_scene_workspace(const vl::SceneLayout& l, void* workspace, size_t workspace_bytes) {
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < l.bytes)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "scene view workspace must be 256-byte aligned and >= %zu bytes", l.bytes);
+    return VMAPSTEP_OK;
+}
+
+static vv::ViewArgs scene_args(const vmapstep_view_cfg* c, const vl::SceneGroup* g, int n_groups, const vl::SceneLayout& l, const float* boxes,
+                               void* workspace) {
+    vv::ViewArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.cam.fx = c->fx; a.cam.fy = c->fy; a.cam.cx = c->cx; a.cam.cy = c->cy;
+    std::memcpy(a.cam.T, c->t_wc, sizeof(a.cam.T));
+    a.cam.min_depth = c->min_depth; a.cam.width = c->width; a.cam.height = c->height; a.cam.samples = 0;
+    a.n_obj = l.n_obj; a.pix_begin = c->pix_begin; a.pix_end = c->pix_end; a.nb = vl::view_blocks(c->pix_begin, c->pix_end);
+    a.boxes = boxes;
+    char* ws = static_cast<char*>(workspace);
+    a.wimg = ws;
+    a.blk = reinterpret_cast<long long*>(ws + l.off_blk);
+    a.plan = reinterpret_cast<int*>(ws + l.off_plan);
+    int end = 0;
+    for (int i = 0; i < vv::kViewMaxGroups; ++i) {
+        if (i < n_groups) end += g[i].n_obj;
+        a.g_end[i] = end;
+        a.g_samples[i] = i < n_groups ? g[i].samples : 1;
+        a.g_per[i] = 1;
+    }
+    return a;
+}
+
+int vmapstep_scene_view_workspace_bytes(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    vl::SceneGroup g[vv::kViewMaxGroups];
+    int n_obj;
+    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
+    *bytes = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_scene_view_count(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, const float* boxes,
+                              int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    vl::SceneGroup g[vv::kViewMaxGroups];
+    int n_obj;
+    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
+    if (!boxes || !offsets) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
+    const vl::SceneLayout l = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end);
+    if (int rc = check_scene_workspace(l, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    vv::ViewArgs a = scene_args(cfg, g, n_groups, l, boxes, workspace);
+    a.offsets = reinterpret_cast<long long*>(offsets);
+    return vl::scene_view_count(a, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_scene_view_render(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups,
+                               const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                               void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                               float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    vl::SceneGroup g[vv::kViewMaxGroups];
+    int n_obj;
+    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
+    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: n_pairs=%lld", (long long)n_pairs);
+    if (!offsets_host) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
+    if (offsets_host[0] != 0 || offsets_host[n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: offsets must run from 0 to n_pairs");
+    for (int k = 0; k < n_obj; ++k)
+        if (offsets_host[k + 1] < offsets_host[k]) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: offsets decrease at object %d", k);
+    // every pair count is <= n_pairs < 2^63 / 64 only if n_pairs is sane: bound it before the products below
+    if (n_pairs >= (1ll << 31)) return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: samples of all groups < 2^31 (n_pairs=%lld): render the pixel range in bands", (long long)n_pairs);
+    const vl::ScenePlan plan = vl::scene_plan_host(reinterpret_cast<const long long*>(offsets_host), g, n_groups);
+    if (plan.samples >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: samples of all groups < 2^31 (%lld): render the pixel range in bands", plan.samples);
+    for (int32_t i = 0; i < n_groups; ++i) {
+        if (int rc = check_params(groups[i].params, "params", false)) return rc;
+        if (!groups[i].pe_scale || !groups[i].pe_scale->ptr) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: pe_scale of group %d is null", (int)i);
+    }
+    if (!boxes || !centers || !offsets || !depth || !color || !opacity || !instance || !overflow ||
+        (n_pairs > 0 && (!pairs || !sample_occ || !sample_rgb)))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
+    const vl::SceneLayout l = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end);
+    if (int rc = check_scene_workspace(l, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    vv::ViewArgs a = scene_args(cfg, g, n_groups, l, boxes, workspace);
+    a.centers = centers;
+    a.offsets = const_cast<long long*>(reinterpret_cast<const long long*>(offsets));
+    a.pairs = static_cast<vg::Pair*>(pairs); a.cap = n_pairs;
+    a.occ = sample_occ; a.rgb = sample_rgb;
+    a.depth = depth; a.color = color; a.opacity = opacity; a.instance = instance; a.overflow = overflow;
+    for (int i = 0; i < n_groups; ++i) { a.g_shift[i] = plan.shift[i]; a.g_per[i] = plan.per[i]; }
+    if (int rc = vl::scene_view_emit(a, st)) return rc;
+    // the field pass, group by group.  Each launch gets the GROUP's argument block: its objects alone (object index, centres, scales,
+    // offsets and images start at the group's first object), its sample count as cam.samples, its plan entries, and occ / rgb placed so
+    // that pair * samples addresses the group's section (integer arithmetic: the address of element g_shift of the buffers)
+    int k0 = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        const vmapstep_view_group& q = groups[i];
+        vv::ViewArgs b = a;
+        b.n_obj = q.n_obj; b.cam.samples = q.samples;
+        b.centers = centers + 3 * k0; b.offsets = a.offsets + k0;
+        b.scale = q.pe_scale->ptr; b.scale_so = q.pe_scale->obj_stride;
+        b.wimg = static_cast<char*>(workspace) + l.off_img[i];
+        b.plan = a.plan + 4 * plan.first[i];
+        b.occ = reinterpret_cast<float*>(reinterpret_cast<intptr_t>(sample_occ) + plan.shift[i] * (long long)sizeof(float));
+        b.rgb = reinterpret_cast<float*>(reinterpret_cast<intptr_t>(sample_rgb) + 3 * plan.shift[i] * (long long)sizeof(float));
+        vk::StepArgs pk;
+        std::memset(&pk, 0, sizeof(pk));
+        pk.n_obj = q.n_obj; pk.hidden = q.hidden; pk.prep_steps = 0;
+        for (int t = 0; t < VMAPSTEP_NUM_FC; ++t) pk.fc[t] = {q.params->fc[t].ptr, q.params->fc[t].obj_stride};
+        pk.pe_B = {q.params->pe_B.ptr, q.params->pe_B.obj_stride};
+        pk.wimg = reinterpret_cast<float*>(const_cast<char*>(b.wimg));
+        if (int rc = vl::scene_field(pk, b, plan.entries[i], st)) return rc;
+        k0 += q.n_obj;
+    }
+    return vl::scene_view_composite(a, st);
+}
+
 // ---- frame ingest ------------------------------------------------------------------------------------------------------------------
 static int check_ingest_ids(int32_t max_ids) {
     if (max_ids < 2 || max_ids > vi::kMaxIds)

@@ -186,12 +186,25 @@ class HipMapper:
         return res, res_bg
 
     # ---- looking at the map -----------------------------------------------------------------------------------
-    def render_view(self, boxes, t_wc, intrinsics, width, height, centers=None, **kw):
+    def render_view(self, boxes, t_wc, intrinsics, width, height, centers=None, background_box=None, background_samples=48,
+                    background_center=None, **kw):
         """Depth, colour, opacity and instance images of the object stack from the camera-to-world pose ``t_wc``: ``render.render_view``
         over the live slab (no copy).  ``boxes`` / ``centers``: one box (``None`` = skip the object) and one ``obj_center`` per object,
-        in ``add_object`` order; the keywords are ``render_view``'s (samples, min_depth, pixel_range, budget_bytes, return_samples)."""
+        in ``add_object`` order; the keywords are ``render_view``'s (samples, min_depth, pixel_range, budget_bytes, return_samples).
+
+        ``background_box``: also render the attached background model inside this box (the room) with ``background_samples`` samples
+        per hit, in the same image: ``render.render_view_groups`` of the object stack and the background's one-object stack as the
+        last group, whose instance index is the number of objects.  ``background_center``: its field-frame centre (default zeros)."""
         from . import render
-        return render.render_view(self, boxes, t_wc, intrinsics, width, height, centers=centers, **kw)
+        if background_box is None:
+            return render.render_view(self, boxes, t_wc, intrinsics, width, height, centers=centers, **kw)
+        if self.bg is None:
+            raise RuntimeError("render_view(background_box=...): attach_background() first")
+        b = self.bg
+        groups = [render.FieldGroup(self, boxes, centers, kw.pop("samples", 16)),
+                  render.FieldGroup((b["views"][:14], b["views"][14], b["scale"]), [background_box],
+                                    None if background_center is None else [background_center], background_samples)]
+        return render.render_view_groups(groups, t_wc, intrinsics, width, height, **kw)
 
     def check_flags(self, res: step.StepResult):
         """Host-side look at the device flags of a frame (the reference exits on 'loss explode', render_rays.py:88-90)."""

@@ -74,7 +74,7 @@ class Trainer:
     @torch.no_grad()
     def render_view(self, bound, obj_center, t_wc, intrinsics, width, height, **kw):
         """This object alone seen from the camera-to-world pose ``t_wc``: ``render.render_view`` with one field, its box ``bound``
-        (anything with .center, .R, .extent) and its ``obj_center``.  Hidden width 32, GPU only."""
+        (anything with .center, .R, .extent) and its ``obj_center``.  Any hidden width 32, 64, ..., 256; GPU only."""
         from . import render
         return render.render_view([self], [bound], t_wc, intrinsics, width, height, centers=[obj_center], **kw)
 
