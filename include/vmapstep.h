@@ -571,6 +571,82 @@ int vmapstep_ingest_frame(const vmapstep_ingest_cfg* cfg, const void* rgb, const
                           void* out_rgbx, float* out_depth, int32_t* out_inst, int32_t* rows_out,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- instance filter: what becomes of every instance id of a ScanNet frame, given the boxes registered so far ---------------------
+ * What the reference's box_filter does on the host per frame (utils.py:112-208, called from dataset.py:249-264), one full-frame pass
+ * per instance there.  Inputs as the image files hold them, row-major [height][width], DEVICE pointers: depth uint16 or float32
+ * (cfg.depth_f32); inst and sem uint16 or int32, both the same type (cfg.label_i32).  The pose t_wc (row-major 4 x 4, camera to
+ * world) and the intrinsics travel in cfg.
+ *
+ * The contract (u = column index, v = row index).  id = raw + id_shift; ids lie in [0, max_ids) (table row = id); pixels with any
+ * other id are counted in `overflow`.  depth = float32(raw) * depth_scale, 0 where that exceeds max_depth; a pixel is valid iff
+ * depth > 0.  Its world point is t_wc . ((u - cx) / fx . d, (v - cy) / fy . d, d, 1) in float32, every product that feeds a sum fused
+ * (csrc/filter_rules.h is the definition).  A pixel is in the eroded mask of its id iff every in-image pixel of the
+ * (2 erode_radius + 1)^2 window around it carries the same id.  box_table (DEVICE float32 [max_ids][16]) holds per id the centre,
+ * three unit axes, three half extents and a flag (non-zero: the id is known); a point is inside iff |(p - centre) . axis| <= half
+ * extent on all three axes.  Per id: pixels, class_min / class_max over sem, valid, inside (valid pixels inside the id's box; 0 for
+ * an id that is not known), eroded, eroded_valid.  Status, first match:
+ *   VMAPSTEP_FILTER_MIXED        class_min != class_max
+ *   VMAPSTEP_FILTER_BACKGROUND   the class is one of background_classes[0 .. n_background), or the id is 0
+ *   VMAPSTEP_FILTER_FEW_POINTS   valid <= min_points
+ *   VMAPSTEP_FILTER_UNSURE       the id is known and inside == 0
+ *   VMAPSTEP_FILTER_MERGED       the id is known and inside > 0
+ *   VMAPSTEP_FILTER_SMALL        the id is new and eroded < min_pixels
+ *   VMAPSTEP_FILTER_NEW          the id is new otherwise
+ * (VMAPSTEP_FILTER_ABSENT: no pixel carries the id; VMAPSTEP_FILTER_NEW_NO_BOX is never written by the library: the caller patches
+ * it into `status` when the cloud of a NEW id turns out to have no box.)
+ *
+ * vmapstep_filter_stats (filter_init, filter_stats, filter_decide) fills `status` (DEVICE int32 [max_ids]) and rows_out (DEVICE int32
+ * [4 + max_ids * 8]): n_rows, overflow, 0, 0, then n_rows rows of (id, status, class, pixels, valid, inside, eroded, eroded_valid) in
+ * ascending id.  vmapstep_filter_emit (filter_count, filter_scan, filter_emit), on the same workspace after it, writes in pixel order
+ * the voxel keys of the valid eroded pixels of NEW ids and of the valid inside pixels of MERGED ids into keys_out (DEVICE uint64
+ * [width * height]), and rows_out[2] = the number of keys, rows_out[3] = out_of_grid.  The key of a point: per axis
+ * k = floor(p / voxel_size); (id << 48) | (kx + 32768) << 32 | (ky + 32768) << 16 | (kz + 32768); a point with a k outside
+ * [-32768, 32767] is counted in out_of_grid and has no key.  vmapstep_filter_write writes labels_out (DEVICE int32 [H][W]) from
+ * `status` as the caller left it: id for NEW; -1 for UNSURE; for MERGED -1 where the pixel is valid and outside the box, else id; 0
+ * otherwise.  vmapstep_voxel_points decodes sorted keys: points (DEVICE float32 [n_keys][3]) = the centres of the voxels,
+ * k * voxel_size + voxel_size / 2 fused, and per segment [offsets[s], offsets[s + 1]) (DEVICE int64 [n_seg + 1]) the minimum and the
+ * maximum of its points' coordinates in bounds (DEVICE float32 [n_seg][6]).
+ * All combining is integer (sum, minimum, maximum) and keys are written in pixel order: the output is bit-identical from call to call.
+ *
+ * Everything is enqueued on `stream`, nothing waits.  Refused before anything is enqueued: null or inconsistent arguments
+ * (VMAPSTEP_ERR_ARGUMENT); width or height above 4095, max_ids outside [2, 32767], erode_radius outside [0, 8], more than 64 classes
+ * (VMAPSTEP_ERR_UNSUPPORTED); a workspace that is not 256-byte aligned or smaller than vmapstep_filter_workspace_bytes(cfg)
+ * (VMAPSTEP_ERR_WORKSPACE). */
+#define VMAPSTEP_FILTER_MAX_CLASSES 64
+#define VMAPSTEP_FILTER_ROW_INTS 8
+#define VMAPSTEP_FILTER_HEAD_INTS 4
+#define VMAPSTEP_FILTER_BOX_FLOATS 16
+#define VMAPSTEP_FILTER_ABSENT 0
+#define VMAPSTEP_FILTER_NEW 1
+#define VMAPSTEP_FILTER_MERGED 2
+#define VMAPSTEP_FILTER_UNSURE 3
+#define VMAPSTEP_FILTER_BACKGROUND 4
+#define VMAPSTEP_FILTER_FEW_POINTS 5
+#define VMAPSTEP_FILTER_SMALL 6
+#define VMAPSTEP_FILTER_MIXED 7
+#define VMAPSTEP_FILTER_NEW_NO_BOX 8
+typedef struct vmapstep_filter_cfg {
+    int32_t width, height;
+    int32_t depth_f32;             /* depth: 0 = uint16, 1 = float32 */
+    int32_t label_i32;             /* inst and sem: 0 = uint16, 1 = int32 */
+    float depth_scale, max_depth;
+    float fx, fy, cx, cy;
+    float t_wc[16];
+    float voxel_size;
+    int32_t id_shift, min_pixels, min_points, erode_radius, max_ids, n_background;
+    int32_t background_classes[VMAPSTEP_FILTER_MAX_CLASSES];
+} vmapstep_filter_cfg;
+
+int vmapstep_filter_workspace_bytes(const vmapstep_filter_cfg* cfg, size_t* bytes);
+int vmapstep_filter_stats(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const void* sem, const float* box_table,
+                          int32_t* status, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_filter_emit(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const int32_t* status, uint64_t* keys_out,
+                         int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_filter_write(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const float* box_table,
+                          const int32_t* status, int32_t* labels_out, void* stream);
+int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* offsets, int32_t n_seg, float voxel_size,
+                          float* points, float* bounds, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

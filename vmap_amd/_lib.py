@@ -124,6 +124,24 @@ INGEST_MAX_CLASSES = 64
 INGEST_ROW_INTS = 8                        # id, status, count, box[4], class
 INGEST_ABSENT, INGEST_KEPT, INGEST_BACKGROUND, INGEST_SMALL, INGEST_ZERO_MARGIN, INGEST_MIXED = range(6)
 
+class FilterCfg(ctypes.Structure):
+    """vmapstep_filter_cfg: the frame shape, the input types, the camera and the rules of the vmapstep_filter_* calls of one frame."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("depth_f32", ctypes.c_int32), ("label_i32", ctypes.c_int32),
+                ("depth_scale", ctypes.c_float), ("max_depth", ctypes.c_float),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("t_wc", ctypes.c_float * 16), ("voxel_size", ctypes.c_float),
+                ("id_shift", ctypes.c_int32), ("min_pixels", ctypes.c_int32), ("min_points", ctypes.c_int32),
+                ("erode_radius", ctypes.c_int32), ("max_ids", ctypes.c_int32), ("n_background", ctypes.c_int32),
+                ("background_classes", ctypes.c_int32 * 64)]
+
+
+FILTER_MAX_CLASSES = 64
+FILTER_ROW_INTS = 8                        # id, status, class, pixels, valid, inside, eroded, eroded_valid
+FILTER_HEAD_INTS = 4                       # n_rows, overflow, n_keys, out_of_grid
+FILTER_BOX_FLOATS = 16                     # centre, three axes, three half extents, known flag
+FILTER_MAX_IDS = 32767
+FILTER_MAX_RADIUS = 8
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -138,6 +156,7 @@ EXPORTS = (
     "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
     "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",
     "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame",
+    "vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write", "vmapstep_voxel_points",
 )
 
 _libs = {}
@@ -261,6 +280,18 @@ def load(path=None):
     lib.vmapstep_ingest_frame.argtypes = [ctypes.POINTER(IngestCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_filter_workspace_bytes.argtypes = [ctypes.POINTER(FilterCfg), ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_filter_stats.argtypes = [ctypes.POINTER(FilterCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_filter_emit.argtypes = [ctypes.POINTER(FilterCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_filter_write.argtypes = [ctypes.POINTER(FilterCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_voxel_points.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
+               "vmapstep_voxel_points"):
+        getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
                "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",
                "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",

@@ -366,7 +366,7 @@ def _search(be, bounds=None):
     return pack
 
 
-def _assemble(row, n_points):
+def _assemble(row, n_points, min_extent=MIN_EXTENT):
     """One BoundingBox (or None) from a result row of _search."""
     if n_points < 4:
         return None
@@ -380,19 +380,20 @@ def _assemble(row, n_points):
     R = axes.T.copy()
     if np.linalg.det(R) < 0:
         R[:, 2] = -R[:, 2]
-    return BoundingBox(center=centre, R=R, extent=np.maximum(raw[order], MIN_EXTENT))
+    return BoundingBox(center=centre, R=R, extent=np.maximum(raw[order], min_extent))
 
 
-def oriented_bounds(points, offsets=None, backend=None, bounds=None, return_info=False):
+def oriented_bounds(points, offsets=None, backend=None, bounds=None, return_info=False, min_extent=MIN_EXTENT):
     """A small-volume oriented box of every segment of ``points`` ([N, 3]; ``offsets`` [n + 1], default one segment) as a list of
     ``BoundingBox`` (centre, R with the box axes as columns, full extents ascending and >= MIN_EXTENT) or ``None`` (fewer than 4
     points, or flat to rounding).  ``backend``: 'hip' (default for a device tensor) or 'numpy' (default otherwise).  ``bounds``
-    [n, 6] float32: the coordinate minimum and maximum of every segment if already known (saves one pass).  With ``return_info``
+    [n, 6] float32: the coordinate minimum and maximum of every segment if already known (saves one pass).  ``min_extent``: the
+    floor of every extent (the reference's 0.10; 0.0 leaves the found box as it is).  With ``return_info``
     also a dict of per-segment arrays: 'coarse_volume' (the best of the coarse set), 'volume' (the found box before clamping)."""
     be = _backend(points, offsets, backend)
     pack = _search(be, None if bounds is None else torch.as_tensor(bounds, dtype=torch.float32))
     counts = np.diff(be.off_h)
-    boxes = [_assemble(pack[o], int(counts[o])) for o in range(be.n_obj)]
+    boxes = [_assemble(pack[o], int(counts[o]), float(min_extent)) for o in range(be.n_obj)]
     if return_info:
         return boxes, {"coarse_volume": pack[:, 18].copy(), "volume": pack[:, 19].copy()}
     return boxes

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 
 namespace vk { struct WsArgs; }
 struct vmapstep_ingest_cfg;
+struct vmapstep_filter_cfg;
 
 namespace vl {
 
@@ -117,5 +118,18 @@ int scene_view_composite(const vv::ViewArgs& a, hipStream_t st);
 // The workspace is vl::ingest_layout's; rows_out holds 2 + max_ids * 8 int32.  inst / sem may be null (no labels / class 0 everywhere).
 int ingest_frame(const vmapstep_ingest_cfg& cfg, const void* rgb, const void* depth, const void* inst, const void* sem, void* out_rgbx,
                  float* out_depth, int* out_inst, int* rows_out, void* workspace, hipStream_t st);
+
+// k_filter.hip: the instance filter (filter_kernels.h).  The workspace is vl::filter_layout's; rows_out holds 4 + max_ids * 8 int32,
+// status max_ids int32, box_table max_ids * 16 float32, keys_out width * height uint64.
+// filter_init, filter_stats, filter_decide:
+int filter_stats(const vmapstep_filter_cfg& cfg, const void* depth, const void* inst, const void* sem, const float* box_table, int* status,
+                 int* rows_out, void* workspace, hipStream_t st);
+// filter_count, filter_scan, filter_emit, on the workspace filter_stats left:
+int filter_emit(const vmapstep_filter_cfg& cfg, const void* depth, const void* inst, const int* status, unsigned long long* keys_out,
+                int* rows_out, void* workspace, hipStream_t st);
+int filter_write(const vmapstep_filter_cfg& cfg, const void* depth, const void* inst, const float* box_table, const int* status, int* labels_out,
+                 hipStream_t st);
+int voxel_points(const unsigned long long* keys, long long n_keys, const long long* offsets, int n_seg, float voxel, float* points, float* bounds,
+                 hipStream_t st);
 
 }  // namespace vl

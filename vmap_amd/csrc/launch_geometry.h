@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view and ingest families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest and filter families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -55,6 +55,24 @@ constexpr int kTile = 64;                  // ingest_write transposes kTile x kT
 constexpr int kMaxIds = 65537;             // every uint16 label and -1
 constexpr int kMaxSide = 4095;             // the sampler's own limit on width and height
 }  // namespace vi
+
+namespace vf {
+constexpr int kFilterWG = 256;             // every filter kernel but filter_decide and filter_scan
+constexpr int kTileW = 64;                 // filter_stats: a workgroup owns kTileW x kTileH pixels (a wave: 64 columns of one row)
+constexpr int kTileH = 16;
+constexpr int kMaxRadius = 8;              // erode_radius <= this: the halo of the LDS tile
+constexpr int kHaloW = kTileW + 2 * kMaxRadius;
+constexpr int kHaloH = kTileH + 2 * kMaxRadius;
+constexpr int kSlots = 64;                 // ids the LDS table of one filter_stats workgroup holds (a power of two)
+constexpr int kProbes = 4;
+constexpr int kTableInts = 8;              // a row of the global table: pixels, class min, class max, valid, inside, eroded, eroded_valid, unused
+constexpr int kReplicas = 8;               // copies of the global table, as vi::kReplicas
+constexpr int kDecideWG = 1024;            // the single workgroup of filter_decide and of filter_scan
+constexpr int kPixPer = 4;                 // consecutive pixels per lane of filter_count / _emit / _write
+constexpr int kPixBlock = kFilterWG * kPixPer;
+constexpr int kMaxIds = 32767;
+constexpr int kMaxSide = 4095;
+}  // namespace vf
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -256,5 +274,21 @@ inline IngestLayout ingest_layout(int max_ids) {
     return l;
 }
 inline int ingest_stats_blocks(int width, int height) { return (int)ceil_div((long long)width * height, vi::kStatsPix); }
+
+// Instance filter.  The workspace: the overflow word, the statistics of every id (int32 [vf::kReplicas][max_ids][vf::kTableInts], row =
+// shifted id), one byte of flags per pixel (valid, inside, eroded: what filter_stats found and filter_emit selects by) and per block
+// of vf::kPixBlock pixels of filter_count an (emitted, out of grid) pair of int32, the first of which filter_scan turns into its prefix.
+inline int filter_pix_blocks(int width, int height) { return (int)ceil_div((long long)width * height, vf::kPixBlock); }
+struct FilterLayout {
+    size_t off_table, off_flags, off_blk, bytes;
+};
+inline FilterLayout filter_layout(int max_ids, int width, int height) {
+    FilterLayout l;
+    l.off_table = 256;
+    l.off_flags = l.off_table + ws_up((size_t)vf::kReplicas * max_ids * vf::kTableInts * sizeof(int));
+    l.off_blk = l.off_flags + ws_up((size_t)width * height);
+    l.bytes = l.off_blk + ws_up((size_t)filter_pix_blocks(width, height) * 2 * sizeof(int));
+    return l;
+}
 
 }  // namespace vl

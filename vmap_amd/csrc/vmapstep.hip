@@ -1068,6 +1068,76 @@ int vmapstep_ingest_frame(const vmapstep_ingest_cfg* cfg, const void* rgb, const
                             workspace, static_cast<hipStream_t>(stream));
 }
 
+// ---- instance filter ---------------------------------------------------------------------------------------------------------------
+static int check_filter_cfg(const vmapstep_filter_cfg* cfg) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "filter: cfg is null");
+    if (cfg->width < 1 || cfg->height < 1 || cfg->n_background < 0 || (cfg->depth_f32 | cfg->label_i32) & ~1)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "filter: width=%d height=%d n_background=%d depth_f32=%d label_i32=%d", cfg->width, cfg->height,
+                    cfg->n_background, cfg->depth_f32, cfg->label_i32);
+    if (!std::isfinite(cfg->depth_scale) || std::isnan(cfg->max_depth) || !(cfg->voxel_size > 0.0f) || !std::isfinite(cfg->voxel_size))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "filter: depth_scale must be finite, max_depth a number, voxel_size finite and > 0");
+    if (cfg->width > vf::kMaxSide || cfg->height > vf::kMaxSide || cfg->n_background > VMAPSTEP_FILTER_MAX_CLASSES)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "filter limits: width, height <= %d, n_background <= %d (width=%d height=%d n_background=%d)",
+                    vf::kMaxSide, VMAPSTEP_FILTER_MAX_CLASSES, cfg->width, cfg->height, cfg->n_background);
+    if (cfg->max_ids < 2 || cfg->max_ids > vf::kMaxIds || cfg->erode_radius < 0 || cfg->erode_radius > vf::kMaxRadius)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "filter limits: 2 <= max_ids <= %d, 0 <= erode_radius <= %d (max_ids=%d erode_radius=%d)",
+                    vf::kMaxIds, vf::kMaxRadius, cfg->max_ids, cfg->erode_radius);
+    return VMAPSTEP_OK;
+}
+
+static int check_filter_workspace(const vmapstep_filter_cfg* cfg, const void* workspace, size_t workspace_bytes) {
+    const size_t need = vl::filter_layout(cfg->max_ids, cfg->width, cfg->height).bytes;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "filter workspace must be 256-byte aligned and >= %zu bytes", need);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_filter_workspace_bytes(const vmapstep_filter_cfg* cfg, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_filter_cfg(cfg)) return rc;
+    *bytes = vl::filter_layout(cfg->max_ids, cfg->width, cfg->height).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_filter_stats(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const void* sem, const float* box_table,
+                          int32_t* status, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg || !depth || !inst || !sem || !box_table || !status || !rows_out) return fail(VMAPSTEP_ERR_ARGUMENT, "filter_stats: null argument");
+    if (int rc = check_filter_cfg(cfg)) return rc;
+    if (int rc = check_filter_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::filter_stats(*cfg, depth, inst, sem, box_table, reinterpret_cast<int*>(status), reinterpret_cast<int*>(rows_out), workspace,
+                            static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_filter_emit(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const int32_t* status, uint64_t* keys_out,
+                         int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg || !depth || !inst || !status || !keys_out || !rows_out) return fail(VMAPSTEP_ERR_ARGUMENT, "filter_emit: null argument");
+    if (int rc = check_filter_cfg(cfg)) return rc;
+    if (int rc = check_filter_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::filter_emit(*cfg, depth, inst, reinterpret_cast<const int*>(status), reinterpret_cast<unsigned long long*>(keys_out),
+                           reinterpret_cast<int*>(rows_out), workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_filter_write(const vmapstep_filter_cfg* cfg, const void* depth, const void* inst, const float* box_table,
+                          const int32_t* status, int32_t* labels_out, void* stream) {
+    if (!cfg || !depth || !inst || !box_table || !status || !labels_out) return fail(VMAPSTEP_ERR_ARGUMENT, "filter_write: null argument");
+    if (int rc = check_filter_cfg(cfg)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::filter_write(*cfg, depth, inst, box_table, reinterpret_cast<const int*>(status), reinterpret_cast<int*>(labels_out),
+                            static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* offsets, int32_t n_seg, float voxel_size,
+                          float* points, float* bounds, void* stream) {
+    if (!keys || !offsets || !points || !bounds) return fail(VMAPSTEP_ERR_ARGUMENT, "voxel_points: null argument");
+    if (n_keys < 0 || n_seg < 1 || !(voxel_size > 0.0f) || !std::isfinite(voxel_size))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "voxel_points: n_keys=%lld n_seg=%d, voxel_size must be finite and > 0", (long long)n_keys, n_seg);
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::voxel_points(reinterpret_cast<const unsigned long long*>(keys), n_keys, reinterpret_cast<const long long*>(offsets), n_seg,
+                            voxel_size, points, bounds, static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

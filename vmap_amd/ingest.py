@@ -10,7 +10,8 @@ the current stream; the read of the small object table is its only synchronisati
 With ``background_classes=()``, ``min_box=-1`` and ``sem=None`` the same call does the second half of ``ScanNet.__getitem__``
 (dataset.py:266-274) on a label image that ``box_filter`` has already merged - on the assumption that ``cv2.boundingRect`` over all
 external contours is the mask's min / max extent plus one, which could not be checked against OpenCV where this was written.
-Reading and decoding the image files, ScanNet's stateful ``box_filter`` / ``track_instance`` and the keyframe policy stay with the caller.
+``box_filter`` itself is ``vmap_amd.instances.InstanceFilter.put``, whose ``labels`` go straight into this call.  Reading and decoding
+the image files, ScanNet's ``track_instance`` and the keyframe policy stay with the caller.
 """
 from __future__ import annotations
 
