@@ -76,6 +76,9 @@ typedef struct vmapstep_tuning {
                                    /* gradient summed with one butterfly per value (A/B: same bits either way)        */
                                    /* bit 4 = the former order of its global loads: B_layer.weight behind the image   */
                                    /* copy, switches / normalisers and z where they are used (A/B: same bits)          */
+                                   /* bit 5 = the former order of its front: all encoding planes split and the        */
+                                   /* backward's cos * pi * 2^f formed in front of the image barrier, none under the   */
+                                   /* forward's matrix chains (A/B: same bits)                                         */
 } vmapstep_tuning;
 
 typedef struct vmapstep_shape {

@@ -14,10 +14,30 @@ int main_v(const vk::StepArgs& a, hipStream_t st) {
     VL_LAUNCH_MAIN(kern, dim3(grid), dim3(vk::kWG), vk::Img32s::LDS_BYTES, st, a);
     return launched("step_main_s32");
 }
+#ifdef VMAPSTEP_AB
+template <bool MULTI, bool W3, bool B6>
+int main_of(const vk::StepArgs& a, hipStream_t st) {
+    auto kern = vk::step_main_s32_of<MULTI, W3, B6>;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), vk::Img32s::LDS_BYTES, "step_main_s32")) return rc;
+    const int grid = a.xcd_affine ? 8 * ((a.n_obj + 7) / 8) * a.NW : a.n_obj * a.NW;
+    VL_LAUNCH_MAIN(kern, dim3(grid), dim3(vk::kWG), vk::Img32s::LDS_BYTES, st, a);
+    return launched("step_main_s32");
+}
+#endif
 template <bool BWD, bool STAMPS>
 int main_bs(const vk::StepArgs& a, hipStream_t st) {
     const bool multi = a.NW < a.NG;
 #ifdef VMAPSTEP_AB
+    if (a.ab_flags & 4) {                    // tuning.ws_flags bit 5: the former order of the front (training instantiations)
+        if constexpr (BWD && !STAMPS) {
+            if (!(a.ab_flags & 3)) {
+                if (a.weights_bf16) return multi ? main_of<true, false, false>(a, st) : main_of<false, false, false>(a, st);
+                if (a.bwd6) return multi ? main_of<true, true, true>(a, st) : main_of<false, true, true>(a, st);
+                return multi ? main_of<true, true, false>(a, st) : main_of<false, true, false>(a, st);
+            }
+        }
+        return fail(-2, "tuning.ws_flags bit 5 (the former front of step_main_s32): training steps without phase stamps, bit 3 or bit 4");
+    }
     if (a.ab_flags & 2) {                    // tuning.ws_flags bit 4: the former order of the global loads (training instantiations, three-product backward)
         if constexpr (BWD && !STAMPS) {
             if (!a.bwd6 && !(a.ab_flags & 1)) {

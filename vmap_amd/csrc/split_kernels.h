@@ -35,6 +35,9 @@
 #endif
 #include "step_kernels.h"
 #include "wave_reduce.h"
+#ifndef VS_FRONT_PARTS           /* measurement builds only (tests/tools/build_variant.py): what step_main_s32 moves from the front of the image barrier under   */
+#define VS_FRONT_PARTS 15        /* the forward's matrix chains, part by part - bit 0 = the planes of e1[24..47], bit 1 = those of e2, bit 2 = cos * pi * 2^f;   */
+#endif                           /* bit 3 = gap_fill's chunks tied where the source forms them                                                                   */
 
 // Measurement builds only (tests/tools/build_variant.py ... -DVS_ABL=<mask>; results WRONG on purpose - the product never defines it):
 // bit 7: step_finalize_s32 does not rewrite the parameter image; bit 4: only the partial-gradient global stores are skipped; bit 5: the finishing (staged reads, sums, stores) is skipped, the staging writes stay;
@@ -725,10 +728,77 @@ __device__ __forceinline__ void fin_chunk(int j, FinState& st, float (&qp)[4], c
     }
 }
 
+// fwd_chain with a callable: vc(m) is invoked behind matrix instruction m of the chain (6 / 3 per 16-deep step), between scheduling
+// fences; the weight rows of step s + 1 are requested before the matrix instructions of step s, as in fwd_chain.  The operand
+// registers of step s are read when the step is issued, so vc may still be filling those of a LATER step.
+template <bool W3, int NS, class VC>
+__device__ __forceinline__ void fwd_chain_il(f32x16& acc, const char* wrow, const unsigned* xh, const unsigned* xm, const unsigned* xl, VC&& vc) {
+    using I = Img32s;
+    constexpr int PS = W3 ? 6 : 3;
+    u32x4 wh = *reinterpret_cast<const u32x4*>(wrow + I::P_HI), wm = wh, wl = wh;
+    if (W3) {
+        wm = *reinterpret_cast<const u32x4*>(wrow + I::P_MID);
+        wl = *reinterpret_cast<const u32x4*>(wrow + I::P_LO);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        u32x4 nh = wh, nm = wm, nl = wl;
+        if (s + 1 < NS) {
+            nh = *reinterpret_cast<const u32x4*>(wrow + 32 * (s + 1) + I::P_HI);
+            if (W3) {
+                nm = *reinterpret_cast<const u32x4*>(wrow + 32 * (s + 1) + I::P_MID);
+                nl = *reinterpret_cast<const u32x4*>(wrow + 32 * (s + 1) + I::P_LO);
+            }
+        }
+        wv::sched_fence();
+#pragma unroll
+        for (int k = 0; k < PS; ++k) {
+            const u32x4 bh = u32x4{xh[4 * s], xh[4 * s + 1], xh[4 * s + 2], xh[4 * s + 3]};
+            const u32x4 bm = u32x4{xm[4 * s], xm[4 * s + 1], xm[4 * s + 2], xm[4 * s + 3]};
+            const u32x4 bl = u32x4{xl[4 * s], xl[4 * s + 1], xl[4 * s + 2], xl[4 * s + 3]};
+            if (W3) {                                    // smallest terms first: the order of fwd_chain
+                acc = k == 0 ? wv::mfma_bf16(wh, bl, acc) : k == 1 ? wv::mfma_bf16(wl, bh, acc) : k == 2 ? wv::mfma_bf16(wm, bm, acc)
+                    : k == 3 ? wv::mfma_bf16(wh, bm, acc) : k == 4 ? wv::mfma_bf16(wm, bh, acc) : wv::mfma_bf16(wh, bh, acc);
+            } else {
+                acc = k == 0 ? wv::mfma_bf16(wh, bl, acc) : k == 1 ? wv::mfma_bf16(wh, bm, acc) : wv::mfma_bf16(wh, bh, acc);
+            }
+            wv::sched_fence();
+            vc(s * PS + k);
+            wv::sched_fence();
+        }
+        wh = nh; wm = nm; wl = nl;
+    }
+}
+// The three-plane split of register pair i of x (split_planes<., 3>, the same operations) in three chunks: c = 0 the hi plane and its
+// residuals (r), c = 1 the mid plane and its residuals (q) - five VALU instructions each, what fits behind one matrix instruction -
+// and c = 2 the lo plane: one conversion, placed a chunk later so that it does not wait for its operands.  The ties (after(): no
+// instruction) make a chunk's results be formed in it - untied they are placed at their use - and keep the two subtractions
+// apart: packed into one v_pk_add_f32 they cost the matrix chain 13 clocks more than two v_sub_f32.
+struct SplitCarry { float ra, rb, qa, qb; };
+__device__ __forceinline__ void split_pair_chunk(int c, int i, const float* x, unsigned* h, unsigned* m, unsigned* l, SplitCarry& k) {
+    if (c == 0) {
+        const float a = x[2 * i], b = x[2 * i + 1];
+        const unsigned ph = wv::pack_bf16(a, b);
+        h[i] = ph;
+        k.ra = a - bf_lo(ph);
+        k.rb = wv::after(b - bf_hi(ph), k.ra);
+    } else if (c == 1) {
+        const unsigned pm = wv::pack_bf16(k.ra, k.rb);
+        m[i] = pm;
+        k.qa = k.ra - bf_lo(pm);
+        k.qb = wv::after(k.rb - bf_hi(pm), k.qa);
+    } else {
+        l[i] = wv::after_u(wv::pack_bf16(k.qa, k.qb), m[i]);
+    }
+}
+
 // One "gap" of the forward: the ReLU + three-plane split of a layer's 16 outputs (16 half-pair chunks of 6-7 VALU
 // instructions) interleaved with NS 16-deep steps of an encoding half that does not depend on them (6 / 3 matrix
 // instructions per step).  wrowB = the lane's weight row of the hi plane at the first of those steps.
-template <bool W3, int NS>
+// TIED: a chunk's residuals are tied where the source forms them (after(): no instruction).  Untied, the compiler places the
+// subtractions of the first chunk at their use in the second - 3 VALU behind one matrix instruction, 10 behind the next - and packs the
+// second chunk's into one v_pk_add_f32, which costs a matrix chain 13 clocks more than two v_sub_f32.  (false: the former form, OF)
+template <bool W3, int NS, bool TIED = false>
 __device__ __forceinline__ void gap_fill(f32x16& accB, const char* wrowB, const unsigned* xh, const unsigned* xm, const unsigned* xl,
                                          const f32x16& accA, float (&hf)[16], unsigned (&hh)[8], unsigned (&hm)[8], unsigned (&hl)[8]) {
     using I = Img32s;
@@ -766,6 +836,12 @@ __device__ __forceinline__ void gap_fill(f32x16& accB, const char* wrowB, const 
                 const unsigned ph = wv::pack_bf16(a, b);
                 hh[i] = ph;
                 ra[i] = a - bf_lo(ph); rb[i] = b - bf_hi(ph);
+                if (TIED) rb[i] = wv::after(rb[i], ra[i]);
+            } else if (TIED) {
+                const unsigned pm = wv::pack_bf16(ra[i], rb[i]);
+                hm[i] = pm;
+                const float qa = ra[i] - bf_lo(pm);
+                hl[i] = wv::pack_bf16(qa, wv::after(rb[i] - bf_hi(pm), qa));
             } else {
                 const unsigned pm = wv::pack_bf16(wv::after(ra[i], accB[0]), rb[i]);
                 hm[i] = pm;
@@ -807,10 +883,14 @@ __device__ __forceinline__ void stage_get_s(float (&q)[4], const float* stage, i
 // PV (measurement build only): the B_layer.weight gradient with one butterfly per value, the form before wave_reduce.h
 // OL (measurement build only, tuning.ws_flags bit 4): the former order of the global loads, word for word - B_layer.weight read
 // behind the image copy, the per-object switches / normalisers and the sample's z loaded where they are used
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false>
+// OF (measurement build only, tuning.ws_flags bit 5): the former order of the front, word for word - all 36 register pairs of the
+// encoding split into planes and the backward's cos * pi * 2^f factors formed in front of the image barrier, the in_layer / mid1 /
+// cat / mid2 chains bare (step_main_s32_of below)
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false, bool OF = false>
 __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     static_assert(!B6 || (W3 && BWD), "six-product backward: float32 weights, training instantiations");
     constexpr int OLD = OL ? 7 : VS_LOADS_OLD;     // bit 0: B_layer, bit 1: switches / normalisers, bit 2: z
+    constexpr int FP = OF ? 0 : VS_FRONT_PARTS;    // bit 0: e1[24..47], bit 1: e2, bit 2: cfac - under the forward's chains; bit 3: gap_fill tied
     using I = Img32s;
     using F = Flat32;
     constexpr int H = 32;
@@ -921,7 +1001,7 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 
     // ---- encoding (embedding.py:82-91): own directions, octaves by double-angle recurrence ----
     float e1[48], e2[24];          // values of this lane's slots (P-form registers of the two groups)
-    float cfac[11][6];             // cos * pi * 2^f of this lane's directions (backward)
+    float cfac[11][6];             // cos * pi * 2^f of this lane's directions (backward); the bare cosines until the forward scales them
     {
         float amax = 0.0f;
 #pragma unroll
@@ -938,7 +1018,8 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 #pragma unroll
             for (int f = 0; f < 6; ++f) {
                 const float sv = own ? s[f] : 0.0f;
-                cfac[i][f] = own ? c[f] * (kPi * (float)(1 << f)) : 0.0f;
+                if constexpr (!(FP & 4)) cfac[i][f] = own ? c[f] * (kPi * (float)(1 << f)) : 0.0f;
+                else cfac[i][f] = c[f];
                 if (f < 4) e1[4 * i + f] = sv;
                 else e2[2 * i + (f - 4)] = sv;
             }
@@ -948,8 +1029,18 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         e2[22] = hi ? 0.0f : 1.0f; e2[23] = 0.0f;
     }
     unsigned e1h[24], e1m[24], e1l[24], e2h[12], e2m[12], e2l[12];
+    if constexpr (OF) {
     split_planes<48, 3>(e1, e1h, e1m, e1l);
     split_planes<24, 3>(e2, e2h, e2m, e2l);
+    } else {
+        // only what the in_layer chain reads first (16-deep steps 0..2) is split in front of the barrier; the other 24 pairs are
+        // split behind matrix instructions of the in_layer and mid1 chains (fwd_front below)
+        if constexpr (FP & 1)
+            split_planes<24, 3>(reinterpret_cast<const float (&)[24]>(e1), reinterpret_cast<unsigned (&)[12]>(e1h), reinterpret_cast<unsigned (&)[12]>(e1m),
+                                reinterpret_cast<unsigned (&)[12]>(e1l));
+        else split_planes<48, 3>(e1, e1h, e1m, e1l);
+        if constexpr (!(FP & 2)) split_planes<24, 3>(e2, e2h, e2m, e2l);
+    }
     VS_MARK(2);
     __syncthreads();        // parameter image landed (the barrier drains the LDS-DMA), composite buffer zeroed
     // ground truth of the ray this lane composites, the per-object switches and normalisers (two 16-byte loads) and this lane's z:
@@ -978,6 +1069,7 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         const char* wcat = W + I::O_CAT + p31 * I::PIT_CAT + 16 * hi;
         const char* wc = W + I::O_C + p31 * I::PIT_C + 16 * hi;
         zero_acc(acc);                                            // the bias rides in the column of the constant-1 slot
+        if constexpr (OF) {
         fwd_chain<W3, 6>(acc, w, e1h, e1m, e1l);
         zero_acc(accE);
         gap_fill<W3, 3>(accE, wcat + 32 * 2, e1h, e1m, e1l, acc, hf, h1h, h1m, h1l);                 // :59 in_layer -> h1 | :63 x[:emb1] half, steps 0..2
@@ -993,6 +1085,64 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         fwd_chain<W3, 2>(acc, w, h3h, h3m, h3l);
         gap_fill<W3, 1>(accC, wc + 32 * 4, e2h + 8, e2m + 8, e2l + 8, acc, h4, h4h, h4m, h4l);       // :67 mid2 -> h4 | step 2
         fwd_chain<W3, 2>(accC, wc, h4h, h4m, h4l);                                                    // :81 cat((fc4, x[emb1:]))
+        } else {
+        // The in_layer chain (36 / 18 matrix instructions) and the mid1 chain (12 / 6) carry the plane splits the barrier did not wait
+        // for, in the order they are read - pairs 12..23 of the first group (16-deep steps 3..5 of this very chain: a step's four pairs
+        // are complete before its first matrix instruction), then the 12 pairs of the second group (first read by the third gap_fill).
+        // 48 slots, one (float32 weights) or two (bf16 weights) per matrix instruction; pair j takes slots 2 j (its hi plane, behind the
+        // lo plane of pair j - 1: six VALU) and 2 j + 1 (its mid plane: five).
+        constexpr int PS = W3 ? 6 : 3, NM_IN = 6 * PS, NM_FRONT = 8 * PS, NSLOT = 48;
+        static_assert(((2 * 3 + 2) * NM_FRONT) / NSLOT < 3 * PS && ((2 * 7 + 2) * NM_FRONT) / NSLOT < 4 * PS && ((2 * 11 + 2) * NM_FRONT) / NSLOT < 5 * PS,
+                      "the planes of steps 3, 4, 5 are complete before the step is issued");
+        SplitCarry carry[24];
+        const auto split_front = [&](int c, int j) {
+            if (j < 12) { if constexpr (FP & 1) split_pair_chunk(c, 12 + j, e1, e1h, e1m, e1l, carry[j]); }
+            else if constexpr (FP & 2) split_pair_chunk(c, j - 12, e2, e2h, e2m, e2l, carry[j]);
+        };
+        const auto fwd_front = [&](int m) {
+#pragma unroll
+            for (int q = m * NSLOT / NM_FRONT; q < (m + 1) * NSLOT / NM_FRONT; ++q) {
+                const int j = q >> 1;
+                if ((q & 1) == 0) {
+                    if (j > 0) split_front(2, j - 1);
+                    split_front(0, j);
+                } else {
+                    split_front(1, j);
+                    if (j == 23) split_front(2, j);
+                }
+            }
+        };
+        // the backward's cfac = cos * pi * 2^f (the same single multiply; the eleventh direction of the hi = 1 lanes is a dummy): 66
+        // products, a third each behind the matrix instructions of the hidden halves of cat_layer and color_linear and of mid2 (two per
+        // instruction and the moves that park them)
+        const auto cfac_chunk = [&](int m, int nm, int third) {
+#pragma unroll
+            for (int x = third * 22 + m * 22 / nm; x < third * 22 + (m + 1) * 22 / nm; ++x) {
+                const int i = x / 6, f = x % 6;
+                const bool own = i < 10 || hi == 0;
+                const float c = cfac[i][f];
+                cfac[i][f] = wv::after(own ? c * (kPi * (float)(1 << f)) : 0.0f, c);   // formed HERE (untied the product is placed at its use, in the backward)
+            }
+        };
+        fwd_chain_il<W3, 6>(acc, w, e1h, e1m, e1l, fwd_front);
+        zero_acc(accE);
+        gap_fill<W3, 3, (FP & 8) != 0>(accE, wcat + 32 * 2, e1h, e1m, e1l, acc, hf, h1h, h1m, h1l);                 // :59 in_layer -> h1 | :63 x[:emb1] half, steps 0..2
+        w = W + I::O_M1 + p31 * I::PIT_M + 16 * hi;
+        load_bias(acc, SM + I::B_M1, hi);
+        fwd_chain_il<W3, 2>(acc, w, h1h, h1m, h1l, [&](int m) { fwd_front(NM_IN + m); });
+        gap_fill<W3, 3, (FP & 8) != 0>(accE, wcat + 32 * 5, e1h + 12, e1m + 12, e1l + 12, acc, hf, h2h, h2m, h2l);  // :60 mid1 -> h2 | steps 3..5
+        if constexpr (BWD && (FP & 4)) fwd_chain_il<W3, 2>(accE, wcat, h2h, h2m, h2l, [&](int m) { cfac_chunk(m, 2 * PS, 0); });   // :63 cat((fc2, x[:emb1]))
+        else fwd_chain<W3, 2>(accE, wcat, h2h, h2m, h2l);
+        zero_acc(accC);
+        gap_fill<W3, 2, (FP & 8) != 0>(accC, wc + 32 * 2, e2h, e2m, e2l, accE, hf, h3h, h3m, h3l);                  // :64 cat_layer -> h3 | :81 x[emb1:] half, steps 0, 1
+        w = W + I::O_M2 + p31 * I::PIT_M + 16 * hi;
+        load_bias(acc, SM + I::B_M2, hi);
+        if constexpr (BWD && (FP & 4)) fwd_chain_il<W3, 2>(acc, w, h3h, h3m, h3l, [&](int m) { cfac_chunk(m, 2 * PS, 1); });
+        else fwd_chain<W3, 2>(acc, w, h3h, h3m, h3l);
+        gap_fill<W3, 1, (FP & 8) != 0>(accC, wc + 32 * 4, e2h + 8, e2m + 8, e2l + 8, acc, h4, h4h, h4m, h4l);       // :67 mid2 -> h4 | step 2
+        if constexpr (BWD && (FP & 4)) fwd_chain_il<W3, 2>(accC, wc, h4h, h4m, h4l, [&](int m) { cfac_chunk(m, 2 * PS, 2); });   // :81 cat((fc4, x[emb1:]))
+        else fwd_chain<W3, 2>(accC, wc, h4h, h4m, h4l);
+        }
         relu_to(hc, accC);                                        // :81 color_linear
     }
     VS_MARK(3);
@@ -1369,6 +1519,11 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false>
 __global__ __launch_bounds__(kWG, 1) void step_main_s32(const StepArgs a) {
     step_main_s32_body<BWD, MULTI, STAMPS, W3, B6, PV, OL>(a);
+}
+// the former order of the front (OF): training instantiations of the measurement build
+template <bool MULTI, bool W3, bool B6>
+__global__ __launch_bounds__(kWG, 1) void step_main_s32_of(const StepArgs a) {
+    step_main_s32_body<true, MULTI, false, W3, B6, false, false, true>(a);
 }
 
 }  // namespace vk

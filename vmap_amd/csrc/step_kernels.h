@@ -98,6 +98,8 @@ struct StepArgs {
     int ab_flags;                      // measurement build (-DVMAPSTEP_AB) only, hidden 32: bit 0 = the launcher takes the step_main_s32 instantiation that reduces the
                                        // B_layer.weight gradient with one butterfly per value (tuning.ws_flags bit 3; float32 weights, training); no kernel reads it
                                        // bit 1 = ... the instantiation with the former order of the global loads (tuning.ws_flags bit 4; training)
+                                       // bit 2 = ... the instantiation with the former order of the front: every encoding plane split and cos * pi * 2^f formed
+                                       // in front of the image barrier (tuning.ws_flags bit 5; training)
 };
 
 // Sample point `smp` of ray `ray` of object `obj` in the object frame: read from the points tensor (train.py:272 batch_input_pcs),
