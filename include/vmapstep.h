@@ -460,7 +460,9 @@ int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t*
  * instance int32 [width][height] at the pixels of the range.  The pair and sample buffers are outputs too.
  * Limits, refused with VMAPSTEP_ERR_UNSUPPORTED before anything touches a device: hidden 32 only, 1 <= samples <= 64,
  * 1 <= n_obj <= 256, 1 <= width, height <= 16384, n_pairs * samples < 2^31.  Workspace: 256-byte aligned,
- * >= vmapstep_view_workspace_bytes(cfg) (VMAPSTEP_ERR_WORKSPACE otherwise); it depends on n_obj and the pixel range only. */
+ * >= vmapstep_view_workspace_bytes(cfg) (VMAPSTEP_ERR_WORKSPACE otherwise); it depends on n_obj and the pixel range only.
+ * These three calls are the one-group hidden-32 case of the scene calls below - one group {32, cfg->n_obj, cfg->samples, params,
+ * pe_scale} - and run the same implementation; their own are the limits, messages and workspace size (768 plan entries) stated here. */
 #define VMAPSTEP_VIEW_MAX_HITS 16
 typedef struct vmapstep_view_cfg {
     int32_t width, height, samples, n_obj;

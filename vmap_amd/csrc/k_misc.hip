@@ -40,16 +40,6 @@ int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, l
     return launched("field_query");
 }
 
-int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st) {
-    // every object's SPLIT image (step_prep_s32's pack role, zero mask-statistics blocks), then one workgroup per plan entry
-    hipLaunchKernelGGL(vk::step_prep_s32<>, dim3(a.n_obj * vk::kSplitPackBlocks), dim3(vk::kWG), 3 * vk::kWG * sizeof(int), st, pack);
-    if (int rc = launched("step_prep_s32")) return rc;
-    if (entries <= 0) return 0;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(vk::field_query_seg_s32<>), vk::kQuerySplitLds, "field_query_seg_s32")) return rc;
-    hipLaunchKernelGGL(vk::field_query_seg_s32<>, dim3((unsigned)entries), dim3(vk::kWG), vk::kQuerySplitLds, st, a);
-    return launched("field_query_seg_s32");
-}
-
 template <int NB>
 static int launch_seg_gen(const vv::ViewArgs& a, unsigned entries, hipStream_t st) {
     const size_t lds = NB > 4 ? (size_t)NB * 1024 * vk::kWaves * sizeof(float) : 0;               // second activation set (NB > 4)
@@ -59,8 +49,16 @@ static int launch_seg_gen(const vv::ViewArgs& a, unsigned entries, hipStream_t s
     return launched("field_query_seg_gen");
 }
 
-int scene_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st) {
-    if (pack.hidden == 32) return view_field(pack, a, entries, st);
+int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st) {
+    if (pack.hidden == 32) {
+        // every object's SPLIT image (step_prep_s32's pack role, zero mask-statistics blocks), then one workgroup per plan entry
+        hipLaunchKernelGGL(vk::step_prep_s32<>, dim3(a.n_obj * vk::kSplitPackBlocks), dim3(vk::kWG), 3 * vk::kWG * sizeof(int), st, pack);
+        if (int rc = launched("step_prep_s32")) return rc;
+        if (entries <= 0) return 0;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(vk::field_query_seg_s32<>), vk::kQuerySplitLds, "field_query_seg_s32")) return rc;
+        hipLaunchKernelGGL(vk::field_query_seg_s32<>, dim3((unsigned)entries), dim3(vk::kWG), vk::kQuerySplitLds, st, a);
+        return launched("field_query_seg_s32");
+    }
     // every object's float32 image (step_prep's pack role, zero mask-statistics blocks), then one workgroup per plan entry
     hipLaunchKernelGGL(vk::step_prep<>, dim3(a.n_obj * (vk::gen_layout(pack.hidden).imgp / 1024)), dim3(vk::kWG), 3 * vk::kWG * sizeof(int), st, pack);
     if (int rc = launched("step_prep")) return rc;

@@ -58,11 +58,9 @@ int finalize_ws8(const vk::FinalizeArgs& f, const vk::FinalizeHot& h, const int*
 // k_misc.hip: inference query and the frame sampler
 int query_points(int hidden, const vk::StepArgs& pack, const vk::QueryArgs& q, long long n_points, hipStream_t st);
 int sample_frame(const vs::SampleArgs& a, int n_obj, long long rays_per_object, hipStream_t st);   // a.obj_max != null: the split form (two launches)
-// view rendering, the field pass: step_prep_s32's pack of all n_obj images, then field_query_seg_s32 over `entries` plan entries
-int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st);
-// the field pass of ONE group of a scene view: the pack of the group's images (pack.hidden: step_prep_s32 at 32, step_prep wider), then
+// view rendering, the field pass of ONE group: the pack of the group's images (pack.hidden: step_prep_s32 at 32, step_prep wider), then
 // field_query_seg_s32 / field_query_seg_gen<hidden / 32> over the group's `entries` plan entries.  `a` is the group's argument block
-int scene_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st);
+int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entries, hipStream_t st);
 
 // The mesh, evaluation and bounds families below take their block sizes, workspace layouts and launch plans from launch_geometry.h
 // (vl::mesh_layout, nn_layout, nn_plan_host, surface_sample_bytes, clip_box_bytes, unproject_blocks, unproject_layout, obb_chunks).
@@ -105,14 +103,10 @@ int obb_extents(const float* points, const long long* po, int n_obj, const float
 int cloud_moments(const float* points, const long long* po, int n_obj, const float* center, double* moments, hipStream_t st);
 
 
-// k_view.hip: view rendering (view_kernels.h).  The workspace is vl::view_layout's; ViewArgs carries its sections.
+// k_view.hip: view rendering (view_kernels.h).  The workspace is vl::scene_layout's; ViewArgs carries its sections and the field groups.
 int view_count(const vv::ViewArgs& a, hipStream_t st);                           // view_count, view_scan -> a.offsets
-int view_emit(const vv::ViewArgs& a, hipStream_t st);                            // view_emit, view_plan (a.plan_per from view_plan_host)
+int view_emit(const vv::ViewArgs& a, hipStream_t st);                            // view_emit, view_plan (a.g_per from scene_plan_host)
 int view_composite(const vv::ViewArgs& a, hipStream_t st);
-// the scene forms (field groups: ViewArgs::g_*; the workspace is vl::scene_layout's, the plan vl::scene_plan_host's)
-int scene_view_count(const vv::ViewArgs& a, hipStream_t st);
-int scene_view_emit(const vv::ViewArgs& a, hipStream_t st);
-int scene_view_composite(const vv::ViewArgs& a, hipStream_t st);
 
 // k_ingest.hip: frame ingest (ingest_kernels.h): ingest_init, ingest_stats, ingest_decide, ingest_write on `st`, nothing between them.
 // The workspace is vl::ingest_layout's; rows_out holds 2 + max_ids * 8 int32.  inst / sem may be null (no labels / class 0 everywhere).

@@ -163,26 +163,53 @@ inline int obb_chunks(const long long* po, int n_obj, int K) {
     return (int)(c < 1 ? 1 : c > 65535 ? 65535 : c);
 }
 
-// View rendering.  The workspace of a call over the pixels [pix_begin, pix_end): the split parameter image of every object
-// (n_obj x vv::kViewImgBytes, packed by step_prep_s32), one int64 per (object, block of vv::kViewBlock pixels) - the hits of the
-// block, then (after view_scan) their exclusive prefix in (object, block) order - and the launch plan of field_query_seg_s32.
+// View rendering: up to vv::kViewMaxGroups field groups, each with its own hidden width and samples per hit, composited into one image
+// (a view of one group is the plain case).  Objects are numbered through the groups in order.  The workspace of a call over the pixels
+// [pix_begin, pix_end): group after group the parameter images of its objects in the layout its field kernel reads (hidden 32:
+// vv::kViewImgBytes split images, packed by step_prep_s32; wider: view_wide_image_floats float32 images, what vk::gen_layout(hidden).imgp
+// is - asserted in query_kernels.h), then one int64 per (object, block of vv::kViewBlock pixels) - the hits of the block, then (after
+// view_scan) their exclusive prefix in (object, block) order - and the launch plan of the field kernels, `plan_cap` entries.
 inline int view_blocks(long long pix_begin, long long pix_end) { return (int)ceil_div(pix_end - pix_begin, vv::kViewBlock); }
-struct ViewLayout {
-    size_t off_blk, off_plan, bytes;
+struct SceneGroup {
+    int hidden, n_obj, samples;
 };
-constexpr long long kViewWgTarget = 512;                                  // two workgroups per compute unit (2 x 80 KiB of LDS)
-constexpr long long kViewPlanCap = kViewWgTarget + vv::kViewMaxObj;       // entries the plan can hold (every object rounds up once)
-inline ViewLayout view_layout(int n_obj, long long pix_begin, long long pix_end) {
-    ViewLayout l;
-    l.off_blk = ws_up((size_t)n_obj * vv::kViewImgBytes);
-    l.off_plan = l.off_blk + ws_up((size_t)n_obj * view_blocks(pix_begin, pix_end) * sizeof(long long));
-    l.bytes = l.off_plan + ws_up((size_t)kViewPlanCap * 4 * sizeof(int));
+constexpr long long view_wide_image_floats(int H) { return (4ll * H * H + 253ll * H + 72 + 1023) / 1024 * 1024; }
+inline size_t view_group_image_bytes(int hidden) {
+    return hidden == 32 ? (size_t)vv::kViewImgBytes : (size_t)view_wide_image_floats(hidden) * sizeof(float);
+}
+// Plan entries per group.  field_query_seg_s32: two workgroups per compute unit (2 x 80 KiB of LDS).  field_query_seg_gen is
+// __launch_bounds__(kWG, 1) and from hidden 160 holds NB x 16 KiB of LDS: ONE workgroup is resident per compute unit, so 256 entries
+// would fill the chip exactly once and any excess entry (every object rounds up once) would cost a whole second round.  Eight entries
+// per compute unit (as kNnItemsTarget, kObbBlocksTarget) bound that tail by 1/8 of a compute unit's share; an entry has no set-up to
+// amortise (the weights are streamed from L2, nothing is staged per workgroup).
+constexpr long long kViewWgTarget = 512;
+constexpr long long kViewWideWgTarget = 2048;
+inline long long view_group_target(int hidden) { return hidden == 32 ? kViewWgTarget : kViewWideWgTarget; }
+// entries the plan of any scene can hold (every object rounds up once); the single-group hidden-32 entry points of the C ABI keep
+// their documented kViewWgTarget + vv::kViewMaxObj, so the capacity is a value of the layout
+constexpr long long kScenePlanCap = vv::kViewMaxGroups * kViewWideWgTarget + vv::kViewMaxObj;
+struct SceneLayout {
+    size_t off_img[vv::kViewMaxGroups], off_blk, off_plan, bytes;
+    int n_obj, plan_cap;                                                    // objects of all groups; plan entries
+};
+inline SceneLayout scene_layout(const SceneGroup* g, int n_groups, long long pix_begin, long long pix_end, int plan_cap) {
+    SceneLayout l{};
+    size_t at = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        l.off_img[i] = at;
+        at += ws_up((size_t)g[i].n_obj * view_group_image_bytes(g[i].hidden));
+        l.n_obj += g[i].n_obj;
+    }
+    l.off_blk = at;
+    l.off_plan = l.off_blk + ws_up((size_t)l.n_obj * view_blocks(pix_begin, pix_end) * sizeof(long long));
+    l.plan_cap = plan_cap;
+    l.bytes = l.off_plan + ws_up((size_t)plan_cap * 4 * sizeof(int));
     return l;
 }
-// The launch plan of field_query_seg_s32 from the host copy of the pair offsets: one entry (object, first chunk, end chunk) per
-// workgroup, chunks of vv::kViewChunk points, `per` chunks per workgroup chosen so that about kViewWgTarget workgroups exist;
-// view_plan writes the entries on the device by the same formula.  The output does not depend on the plan (a point's value
-// depends on the point alone).
+// The launch plan of one group's field kernel from the host copy of its pair offsets: one entry (object, first chunk, end chunk) per
+// workgroup, chunks of vv::kViewChunk points, `per` chunks per workgroup chosen so that about `target` workgroups exist; view_plan
+// writes the entries on the device by the same formula.  The output does not depend on the plan (a point's value depends on the point
+// alone).
 struct ViewPlan {
     long long per, entries;
 };
@@ -196,50 +223,10 @@ inline ViewPlan view_plan_host_target(const long long* offsets, int n_obj, int s
     for (int k = 0; k < n_obj; ++k) p.entries += ceil_div(ceil_div((offsets[k + 1] - offsets[k]) * samples, vv::kViewChunk), p.per);
     return p;
 }
-inline ViewPlan view_plan_host(const long long* offsets, int n_obj, int samples) {
-    return view_plan_host_target(offsets, n_obj, samples, kViewWgTarget);
-}
-
-// Scene view: up to vv::kViewMaxGroups field groups, each with its own hidden width and samples per hit, composited into one image.
-// Objects are numbered through the groups in order.  The workspace: group after group the parameter images of its objects in the
-// layout its field kernel reads (hidden 32: vv::kViewImgBytes split images; wider: view_wide_image_floats float32 images, what
-// vk::gen_layout(hidden).imgp is - asserted in query_kernels.h), then the block totals and the launch plan as in ViewLayout.
-struct SceneGroup {
-    int hidden, n_obj, samples;
-};
-constexpr long long view_wide_image_floats(int H) { return (4ll * H * H + 253ll * H + 72 + 1023) / 1024 * 1024; }
-inline size_t view_group_image_bytes(int hidden) {
-    return hidden == 32 ? (size_t)vv::kViewImgBytes : (size_t)view_wide_image_floats(hidden) * sizeof(float);
-}
-// Plan entries per group.  field_query_seg_s32 keeps kViewWgTarget.  field_query_seg_gen is __launch_bounds__(kWG, 1) and from
-// hidden 160 holds NB x 16 KiB of LDS: ONE workgroup is resident per compute unit, so 256 entries would fill the chip exactly once
-// and any excess entry (every object rounds up once) would cost a whole second round.  Eight entries per compute unit (as
-// kNnItemsTarget, kObbBlocksTarget) bound that tail by 1/8 of a compute unit's share; an entry has no set-up to amortise (the
-// weights are streamed from L2, nothing is staged per workgroup).
-constexpr long long kViewWideWgTarget = 2048;
-inline long long view_group_target(int hidden) { return hidden == 32 ? kViewWgTarget : kViewWideWgTarget; }
-constexpr long long kScenePlanCap = vv::kViewMaxGroups * kViewWideWgTarget + vv::kViewMaxObj;   // every object rounds up once
-struct SceneLayout {
-    size_t off_img[vv::kViewMaxGroups], off_blk, off_plan, bytes;
-    int n_obj;                                                              // all groups
-};
-inline SceneLayout scene_layout(const SceneGroup* g, int n_groups, long long pix_begin, long long pix_end) {
-    SceneLayout l{};
-    size_t at = 0;
-    for (int i = 0; i < n_groups; ++i) {
-        l.off_img[i] = at;
-        at += ws_up((size_t)g[i].n_obj * view_group_image_bytes(g[i].hidden));
-        l.n_obj += g[i].n_obj;
-    }
-    l.off_blk = at;
-    l.off_plan = l.off_blk + ws_up((size_t)l.n_obj * view_blocks(pix_begin, pix_end) * sizeof(long long));
-    l.bytes = l.off_plan + ws_up((size_t)kScenePlanCap * 4 * sizeof(int));
-    return l;
-}
-// The launch plan of a scene from the host copy of the pair offsets: view_plan_host's formula per group (its own sample count and
-// workgroup target).  The entries of a group are contiguous: scene_view_plan scans them in object order.  `shift`: the groups'
-// sample sections lie one after the other, inside a group pair after pair, so sample s of pair pr (a global pair index) of group g
-// is element pr * samples_g + shift[g] + s of sample_occ.  `samples`: all groups.
+// The launch plan of a view: view_plan_host_target per group (its own sample count and workgroup target).  The entries of a group are
+// contiguous: view_plan scans them in object order.  `shift`: the groups' sample sections lie one after the other, inside a group
+// pair after pair, so sample s of pair pr (a global pair index) of group g is element pr * samples_g + shift[g] + s of sample_occ.
+// `samples`: all groups.
 struct ScenePlan {
     long long per[vv::kViewMaxGroups], entries[vv::kViewMaxGroups], first[vv::kViewMaxGroups], shift[vv::kViewMaxGroups], samples;
 };

@@ -9,11 +9,12 @@
 //   view_emit       the same hit test; rank inside the block from the ballot; one 16-byte pair record (pixel, t_near, dt, 0) per hit,
 //                   ordered by (object, pixel)
 //   view_plan       one workgroup: the launch plan of field_query_seg_s32 (query_split_kernels.h, the hot kernel: the field at every
-//                   sample of every pair) from the device offsets, by the formula of vl::view_plan_host
+//                   sample of every pair) from the device offsets, by the formula of vl::scene_plan_host
 //   view_composite  one lane per pixel: the hit test a third time, the pair index from block prefix + ballot rank, at most
 //                   kViewMaxHits (t_near, dt, sample base, cursor) entries in LDS, merged by repeatedly taking the smallest (t, object)
-// A scene of several field groups (own hidden width and samples per hit each) runs the scene_view_* forms of the same bodies and one
-// field kernel launch per group: field_query_seg_s32 at hidden 32, field_query_seg_gen<NB> (query_kernels.h) at the wider widths.
+// Objects come in up to kViewMaxGroups field groups with their own hidden width and samples per hit (ViewArgs::g_*): the kernels here
+// walk group after group, and the field pass is one field kernel launch per group - field_query_seg_s32 at hidden 32,
+// field_query_seg_gen<NB> (query_kernels.h) at the wider widths.  A view of one group is the case g_end = {n, n, n, n}.
 // The three passes call ONE inline function (view_hit), so they cannot disagree on a hit; nothing blocks combine is a float sum, so the
 // images are bit-identical from call to call and for any split of the pixel range into calls.
 #pragma once
@@ -36,24 +37,7 @@ __device__ __forceinline__ bool view_lane(const ViewArgs& a, long long& pix, vg:
     return live;
 }
 
-// The kernels exist in two forms with ONE body each (the template argument is a compile-time switch, so the single-group form is
-// the code it was): the single-group form (one sample count, cam.samples) and the SCENE form (field groups, ViewArgs::g_*: an object's
-// sample count is its group's, a pair's samples start at pair * S_g + g_shift[g]).
-template <bool SCENE>
-__device__ __forceinline__ int obj_group(const ViewArgs& a, int k) {
-    if constexpr (!SCENE) return 0;
-    int g = 0;
-#pragma unroll
-    for (int i = 0; i < kViewMaxGroups - 1; ++i) g += k >= a.g_end[i] ? 1 : 0;
-    return g;
-}
-template <bool SCENE>
-__device__ __forceinline__ int obj_samples(const ViewArgs& a, int k) {
-    if constexpr (SCENE) return a.g_samples[obj_group<true>(a, k)];
-    return a.cam.samples;
-}
-
-// THE hit test of all three passes (S = the object's sample count)
+// THE hit test of all three passes (S = the sample count of the object's group)
 __device__ __forceinline__ bool view_hit(const ViewArgs& a, const vg::Ray& r, bool live, int k, int S, float& t_near, float& dt) {
     const bool hit = vg::box_segment(r, a.boxes + 15 * k, a.cam.min_depth, S, t_near, dt);
     return live && hit;
@@ -63,19 +47,22 @@ __device__ __forceinline__ int ballot_rank(unsigned long long ballot) {
     return __popcll(ballot & ((1ull << (threadIdx.x & 63)) - 1ull));
 }
 
-template <bool SCENE>
-__device__ __forceinline__ void view_count_body(const ViewArgs& a) {
+// The three passes walk the objects group after group - `for (int g = 0, k = 0; g < kViewMaxGroups; ++g) for (; k < g_end[g]; ++k)` -
+// so that the group's sample count, sample shift and end are loop invariants (the groups past the last one are empty: g_end = n_obj).
+
+__global__ void __launch_bounds__(kViewBlock) view_count(const ViewArgs a) {
     long long pix;
     vg::Ray r;
     const bool live = view_lane(a, pix, r);
-    for (int k = 0; k < a.n_obj; ++k) {
-        float tn, dt;
-        const unsigned long long b = __ballot(view_hit(a, r, live, k, obj_samples<SCENE>(a, k), tn, dt));
-        if (threadIdx.x == 0) a.blk[(long long)k * a.nb + blockIdx.x] = __popcll(b);
+    for (int g = 0, k = 0; g < kViewMaxGroups; ++g) {
+        const int S = a.g_samples[g], end = a.g_end[g];
+        for (; k < end; ++k) {
+            float tn, dt;
+            const unsigned long long b = __ballot(view_hit(a, r, live, k, S, tn, dt));
+            if (threadIdx.x == 0) a.blk[(long long)k * a.nb + blockIdx.x] = __popcll(b);
+        }
     }
 }
-__global__ void __launch_bounds__(kViewBlock) view_count(const ViewArgs a) { view_count_body<false>(a); }
-__global__ void __launch_bounds__(kViewBlock) scene_view_count(const ViewArgs a) { view_count_body<true>(a); }
 
 __global__ void __launch_bounds__(kViewScanWG) view_scan(const ViewArgs a) {
     __shared__ long long wsum[kViewScanWG / 64];
@@ -86,60 +73,62 @@ __global__ void __launch_bounds__(kViewScanWG) view_scan(const ViewArgs a) {
     for (int o = threadIdx.x; o <= a.n_obj; o += kViewScanWG) a.offsets[o] = o < a.n_obj ? a.blk[(long long)o * a.nb] : carry;
 }
 
-template <bool SCENE>
-__device__ __forceinline__ void view_emit_body(const ViewArgs& a) {
+__global__ void __launch_bounds__(kViewBlock) view_emit(const ViewArgs a) {
     long long pix;
     vg::Ray r;
     const bool live = view_lane(a, pix, r);
-    for (int k = 0; k < a.n_obj; ++k) {
-        float tn, dt;
-        const bool hit = view_hit(a, r, live, k, obj_samples<SCENE>(a, k), tn, dt);
-        const long long at = a.blk[(long long)k * a.nb + blockIdx.x] + ballot_rank(__ballot(hit));
-        if (hit && at >= 0 && at < a.cap) a.pairs[at] = vg::Pair{(int)pix, tn, dt, 0};
+    for (int g = 0, k = 0; g < kViewMaxGroups; ++g) {
+        const int S = a.g_samples[g], end = a.g_end[g];
+        for (; k < end; ++k) {
+            float tn, dt;
+            const bool hit = view_hit(a, r, live, k, S, tn, dt);
+            const long long at = a.blk[(long long)k * a.nb + blockIdx.x] + ballot_rank(__ballot(hit));
+            if (hit && at >= 0 && at < a.cap) a.pairs[at] = vg::Pair{(int)pix, tn, dt, 0};
+        }
     }
 }
-__global__ void __launch_bounds__(kViewBlock) view_emit(const ViewArgs a) { view_emit_body<false>(a); }
-__global__ void __launch_bounds__(kViewBlock) scene_view_emit(const ViewArgs a) { view_emit_body<true>(a); }
 
-// one lane per object; the scene form writes the group's own object index (the field kernel of a group sees its objects alone) and
-// cuts by the group's chunks per entry; entries come out in object order, so a group's entries are contiguous
-template <bool SCENE>
-__device__ __forceinline__ void view_plan_body(const ViewArgs& a) {
+// one lane per object; an entry holds the object's index inside its group (the field kernel of a group sees its objects alone) and
+// the group's chunks per entry; entries come out in object order, so a group's entries are contiguous
+__global__ void __launch_bounds__(kViewPlanWG) view_plan(const ViewArgs a) {
     __shared__ int wsum[kViewPlanWG / 64];
     const int k = threadIdx.x;
-    const int g = obj_group<SCENE>(a, k < a.n_obj ? k : 0);
-    const long long per = SCENE ? a.g_per[g] : a.plan_per;
-    const int kg = SCENE && g > 0 ? k - a.g_end[g - 1] : k;
+    int g = 0;
+#pragma unroll
+    for (int i = 0; i < kViewMaxGroups - 1; ++i) g += k < a.n_obj && k >= a.g_end[i] ? 1 : 0;
+    const long long per = a.g_per[g];
+    const int kg = g > 0 ? k - a.g_end[g - 1] : k;
     long long chunks = 0;
-    if (k < a.n_obj) chunks = ((a.offsets[k + 1] - a.offsets[k]) * obj_samples<SCENE>(a, k) + kViewChunk - 1) / kViewChunk;
+    if (k < a.n_obj) chunks = ((a.offsets[k + 1] - a.offsets[k]) * a.g_samples[g] + kViewChunk - 1) / kViewChunk;
     const int mine = (int)((chunks + per - 1) / per);
     int total;
     const int first = vscan::wg_exclusive_scan<kViewPlanWG>(mine, wsum, total);
-    constexpr long long cap = SCENE ? vl::kScenePlanCap : vl::kViewPlanCap;
-    for (int e = 0; e < mine && first + e < cap; ++e) {
+    for (int e = 0; e < mine && first + e < a.plan_cap; ++e) {
         const long long c0 = e * per, c1 = c0 + per < chunks ? c0 + per : chunks;
         int* q = a.plan + 4 * (first + e);
         q[0] = kg; q[1] = (int)c0; q[2] = (int)c1; q[3] = 0;
     }
 }
-__global__ void __launch_bounds__(kViewPlanWG) view_plan(const ViewArgs a) { view_plan_body<false>(a); }
-__global__ void __launch_bounds__(kViewPlanWG) scene_view_plan(const ViewArgs a) { view_plan_body<true>(a); }
 
-template <bool SCENE>
-__device__ __forceinline__ void view_composite_body(const ViewArgs& a) {
+// The one kernel with two instantiations (every single-form build of it measured 4-5 % slower on the one-group view).
+// GROUPS: an entry's object and its group's sample count share one LDS word, e_obj = object << 8 | S (S <= kViewMaxSamples < 2^8) -
+// six arrays, 24 KiB per workgroup, six workgroups per compute unit; a pixel holds an object once, so the words order as the objects
+// do and the (t, object) comparisons take them as they are.  !GROUPS (a view of one group, g_end[0] = n_obj): one flat object loop,
+// the uniform cam.samples, e_obj = object.
+static_assert(kViewMaxSamples < 256, "entry word: sample count in bits 0-7, object above");
+
+template <bool GROUPS>
+__global__ void __launch_bounds__(kViewBlock) view_composite(const ViewArgs a) {
     __shared__ float e_tn[kViewMaxHits][kViewBlock], e_dt[kViewMaxHits][kViewBlock], e_w[kViewMaxHits][kViewBlock];
     __shared__ int e_base[kViewMaxHits][kViewBlock], e_cur[kViewMaxHits][kViewBlock], e_obj[kViewMaxHits][kViewBlock];
-    __shared__ int e_S[SCENE ? kViewMaxHits : 1][kViewBlock];     // scene: the entry's own sample count
     const int lane = threadIdx.x;
     long long pix;
     vg::Ray r;
     const bool live = view_lane(a, pix, r);
     int n = 0;
     bool over = false;
-    for (int k = 0; k < a.n_obj; ++k) {
+    auto object = [&](int k, int S, long long shift) {
         float tn, dt;
-        const int g = obj_group<SCENE>(a, k);
-        const int S = SCENE ? a.g_samples[g] : a.cam.samples;
         const bool hit = view_hit(a, r, live, k, S, tn, dt);
         const long long at = a.blk[(long long)k * a.nb + blockIdx.x] + ballot_rank(__ballot(hit));
         // a pair index outside the object's segment (or the buffers) is never dereferenced
@@ -160,11 +149,19 @@ __device__ __forceinline__ void view_composite_body(const ViewArgs& a) {
             }
             if (slot >= 0) {
                 e_tn[slot][lane] = tn; e_dt[slot][lane] = dt; e_w[slot][lane] = 0.0f;
-                e_base[slot][lane] = SCENE ? (int)(at * S + a.g_shift[g]) : (int)(at * S);
-                e_cur[slot][lane] = 0; e_obj[slot][lane] = k;
-                if constexpr (SCENE) e_S[slot][lane] = S;
+                e_base[slot][lane] = (int)(at * S + shift);
+                e_cur[slot][lane] = 0; e_obj[slot][lane] = GROUPS ? k << 8 | S : k;
             }
         }
+    };
+    if constexpr (GROUPS) {
+        for (int g = 0, k = 0; g < kViewMaxGroups; ++g) {
+            const int S = a.g_samples[g], end = a.g_end[g];
+            const long long shift = a.g_shift[g];
+            for (; k < end; ++k) object(k, S, shift);
+        }
+    } else {
+        for (int k = 0; k < a.n_obj; ++k) object(k, a.cam.samples, 0);
     }
     if (!live) return;
     if (over) atomicAdd(a.overflow, 1);
@@ -175,9 +172,9 @@ __device__ __forceinline__ void view_composite_body(const ViewArgs& a) {
             int best = -1, bobj = 0;
             float bt = 0.0f;
             for (int e = 0; e < n; ++e) {
-                if (e_cur[e][lane] >= (SCENE ? e_S[SCENE ? e : 0][lane] : a.cam.samples)) continue;
-                const float t = vg::sample_depth(e_tn[e][lane], e_dt[e][lane], e_cur[e][lane]);
                 const int o = e_obj[e][lane];
+                if (e_cur[e][lane] >= (GROUPS ? o & 255 : a.cam.samples)) continue;
+                const float t = vg::sample_depth(e_tn[e][lane], e_dt[e][lane], e_cur[e][lane]);
                 if (best < 0 || t < bt || (t == bt && o < bobj)) { best = e; bt = t; bobj = o; }
             }
             if (best < 0) break;
@@ -198,7 +195,7 @@ __device__ __forceinline__ void view_composite_body(const ViewArgs& a) {
     float wbest = 0.0f;
     for (int e = 0; e < n; ++e) {
         const float w = e_w[e][lane];
-        const int o = e_obj[e][lane];
+        const int o = GROUPS ? e_obj[e][lane] >> 8 : e_obj[e][lane];
         if (inst < 0 || w > wbest || (w == wbest && o < inst)) { inst = o; wbest = w; }
     }
     a.depth[pix] = depth;
@@ -206,7 +203,5 @@ __device__ __forceinline__ void view_composite_body(const ViewArgs& a) {
     a.opacity[pix] = opacity;
     a.instance[pix] = inst;
 }
-__global__ void __launch_bounds__(kViewBlock) view_composite(const ViewArgs a) { view_composite_body<false>(a); }
-__global__ void __launch_bounds__(kViewBlock) scene_view_composite(const ViewArgs a) { view_composite_body<true>(a); }
 
 }  // namespace vv

@@ -792,224 +792,117 @@ int vmapstep_cloud_moments(const float* points, int64_t n_points, const int64_t*
 static_assert(sizeof(vmapstep_sample_object) == sizeof(vs::SampleObject), "sample object table layout");
 
 // ---- view rendering ----------------------------------------------------------------------------------------------------------------
-static int check_view_cfg(const vmapstep_view_cfg* c) {
-    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "view: cfg is null");
-    if (c->samples < 1 || c->samples > vv::kViewMaxSamples || c->n_obj < 1 || c->n_obj > vv::kViewMaxObj || c->width < 1 || c->height < 1 ||
-        c->width > 16384 || c->height > 16384)
-        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: 1 <= samples <= %d, 1 <= n_obj <= %d, 1 <= width, height <= 16384 (samples=%d n_obj=%d width=%d height=%d)",
-                    vv::kViewMaxSamples, vv::kViewMaxObj, c->samples, c->n_obj, c->width, c->height);
-    if (c->pix_begin < 0 || c->pix_end < c->pix_begin || c->pix_end > (int64_t)c->width * c->height)
-        return fail(VMAPSTEP_ERR_ARGUMENT, "view: pixel range [%lld, %lld) outside the image", (long long)c->pix_begin, (long long)c->pix_end);
-    if (!(std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy)) || c->fx == 0.0f || c->fy == 0.0f)
-        return fail(VMAPSTEP_ERR_ARGUMENT, "view: intrinsics must be finite with fx, fy != 0");
-    return VMAPSTEP_OK;
-}
-
-static int check_view_workspace(const vmapstep_view_cfg* c, void* workspace, size_t workspace_bytes) {
-    const size_t need = vl::view_layout(c->n_obj, c->pix_begin, c->pix_end).bytes;
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
-        return fail(VMAPSTEP_ERR_WORKSPACE, "view workspace must be 256-byte aligned and >= %zu bytes", need);
-    return VMAPSTEP_OK;
-}
-
-static vv::ViewArgs view_args(const vmapstep_view_cfg* c, const float* boxes, void* workspace) {
-    vv::ViewArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cam.fx = c->fx; a.cam.fy = c->fy; a.cam.cx = c->cx; a.cam.cy = c->cy;
-    std::memcpy(a.cam.T, c->t_wc, sizeof(a.cam.T));
-    a.cam.min_depth = c->min_depth; a.cam.width = c->width; a.cam.height = c->height; a.cam.samples = c->samples;
-    a.n_obj = c->n_obj; a.pix_begin = c->pix_begin; a.pix_end = c->pix_end; a.nb = vl::view_blocks(c->pix_begin, c->pix_end);
-    a.boxes = boxes;
-    const vl::ViewLayout l = vl::view_layout(c->n_obj, c->pix_begin, c->pix_end);
-    char* ws = static_cast<char*>(workspace);
-    a.wimg = ws;
-    a.blk = reinterpret_cast<long long*>(ws + l.off_blk);
-    a.plan = reinterpret_cast<int*>(ws + l.off_plan);
-    return a;
-}
-
-int vmapstep_view_workspace_bytes(const vmapstep_view_cfg* cfg, size_t* bytes) {
-    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
-    if (int rc = check_view_cfg(cfg)) return rc;
-    *bytes = vl::view_layout(cfg->n_obj, cfg->pix_begin, cfg->pix_end).bytes;
-    return VMAPSTEP_OK;
-}
-
-int vmapstep_view_count(const vmapstep_view_cfg* cfg, const float* boxes, int64_t* offsets, void* workspace, size_t workspace_bytes,
-                        void* stream) {
-    if (int rc = check_view_cfg(cfg)) return rc;
-    if (!boxes || !offsets) return fail(VMAPSTEP_ERR_ARGUMENT, "view: null argument");
-    if (int rc = check_view_workspace(cfg, workspace, workspace_bytes)) return rc;
-    VMAPSTEP_ON_STREAM_DEVICE(stream);
-    vv::ViewArgs a = view_args(cfg, boxes, workspace);
-    a.offsets = reinterpret_cast<long long*>(offsets);
-    return vl::view_count(a, static_cast<hipStream_t>(stream));
-}
-
-int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vmapstep_params* params, const vmapstep_tensor* pe_scale,
-                         const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
-                         void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
-                         float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (hidden != 32) return fail(VMAPSTEP_ERR_UNSUPPORTED, "view: hidden=%d, the view renderer implements hidden 32 only", hidden);
-    if (int rc = check_view_cfg(cfg)) return rc;
-    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "view: n_pairs=%lld", (long long)n_pairs);
-    if (n_pairs * cfg->samples >= (1ll << 31))
-        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: n_pairs * samples < 2^31 (n_pairs=%lld samples=%d): render the pixel range in bands",
-                    (long long)n_pairs, cfg->samples);
-    if (int rc = check_params(params, "params", false)) return rc;
-    if (!pe_scale || !pe_scale->ptr || !boxes || !centers || !offsets || !offsets_host || !depth || !color || !opacity || !instance || !overflow ||
-        (n_pairs > 0 && (!pairs || !sample_occ || !sample_rgb)))
-        return fail(VMAPSTEP_ERR_ARGUMENT, "view: null argument");
-    if (offsets_host[0] != 0 || offsets_host[cfg->n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "view: offsets must run from 0 to n_pairs");
-    for (int32_t k = 0; k < cfg->n_obj; ++k)
-        if (offsets_host[k + 1] < offsets_host[k]) return fail(VMAPSTEP_ERR_ARGUMENT, "view: offsets decrease at object %d", (int)k);
-    if (int rc = check_view_workspace(cfg, workspace, workspace_bytes)) return rc;
-    VMAPSTEP_ON_STREAM_DEVICE(stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    vv::ViewArgs a = view_args(cfg, boxes, workspace);
-    a.centers = centers; a.scale = pe_scale->ptr; a.scale_so = pe_scale->obj_stride;
-    a.offsets = const_cast<long long*>(reinterpret_cast<const long long*>(offsets));
-    a.pairs = static_cast<vg::Pair*>(pairs); a.cap = n_pairs;
-    a.occ = sample_occ; a.rgb = sample_rgb;
-    a.depth = depth; a.color = color; a.opacity = opacity; a.instance = instance; a.overflow = overflow;
-    const vl::ViewPlan plan = vl::view_plan_host(reinterpret_cast<const long long*>(offsets_host), cfg->n_obj, cfg->samples);
-    a.plan_per = plan.per;
-    if (int rc = vl::view_emit(a, st)) return rc;
-    vk::StepArgs pk;
-    std::memset(&pk, 0, sizeof(pk));
-    pk.n_obj = cfg->n_obj; pk.hidden = 32; pk.prep_steps = 0;
-    for (int t = 0; t < VMAPSTEP_NUM_FC; ++t) pk.fc[t] = {params->fc[t].ptr, params->fc[t].obj_stride};
-    pk.pe_B = {params->pe_B.ptr, params->pe_B.obj_stride};
-    pk.wimg = static_cast<float*>(workspace);
-    if (int rc = vl::view_field(pk, a, plan.entries, st)) return rc;
-    return vl::view_composite(a, st);
-}
-
-// ---- scene view: field groups of their own width and sample count, one image ---------------------------------------------------------
+// ONE implementation: field groups of their own hidden width and sample count composited into one image.  vmapstep_scene_view_* are
+// its entry points; vmapstep_view_* are the one-group hidden-32 case of them: after their own argument checks (their limits, messages
+// and order are the ABI's) they fill one vmapstep_view_group from the cfg and call the same bodies.
 static_assert(VMAPSTEP_VIEW_MAX_GROUPS == vv::kViewMaxGroups, "one group limit");
+constexpr int kViewFrontPlanCap = vl::kViewWgTarget + vv::kViewMaxObj;      // the 768 plan entries vmapstep_view_workspace_bytes documents
 
-// every limit of the scene section, then the arguments the camera shares with the single-group form; fills g[] and the object total
-static int check_scene(const vmapstep_view_cfg* c, const vmapstep_view_group* groups, int32_t n_groups, vl::SceneGroup* g, int* n_obj) {
-    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: cfg is null");
-    if (n_groups < 1 || n_groups > vv::kViewMaxGroups)
-        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: 1 <= n_groups <= %d (n_groups=%d)", vv::kViewMaxGroups, n_groups);
-    if (!groups) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: groups is null");
-    long long total = 0;
-    for (int32_t i = 0; i < n_groups; ++i) {
-        const vmapstep_view_group& q = groups[i];
-        if (q.hidden < 32 || q.hidden > 256 || q.hidden % 32 != 0 || q.samples < 1 || q.samples > vv::kViewMaxSamples || q.n_obj < 1)
-            return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: hidden a multiple of 32 in [32, 256], 1 <= samples <= %d, n_obj >= 1 "
-                        "(group %d: hidden=%d samples=%d n_obj=%d)", vv::kViewMaxSamples, (int)i, q.hidden, q.samples, q.n_obj);
-        g[i] = vl::SceneGroup{q.hidden, q.n_obj, q.samples};
-        total += q.n_obj;
-    }
-    if (total > vv::kViewMaxObj || c->width < 1 || c->height < 1 || c->width > 16384 || c->height > 16384)
-        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: objects of all groups <= %d, 1 <= width, height <= 16384 (objects=%lld width=%d height=%d)",
-                    vv::kViewMaxObj, total, c->width, c->height);
+// what an entry point hands to the shared bodies, after its own limits
+struct ViewCall {
+    const char* name;                          // the prefix of every message: "view" | "scene view"
+    const vmapstep_view_cfg* cfg;
+    const vmapstep_view_group* groups;
+    int n_groups, plan_cap;
+};
+
+static int check_camera(const char* name, const vmapstep_view_cfg* c) {
     if (c->pix_begin < 0 || c->pix_end < c->pix_begin || c->pix_end > (int64_t)c->width * c->height)
-        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: pixel range [%lld, %lld) outside the image", (long long)c->pix_begin, (long long)c->pix_end);
+        return fail(VMAPSTEP_ERR_ARGUMENT, "%s: pixel range [%lld, %lld) outside the image", name, (long long)c->pix_begin, (long long)c->pix_end);
     if (!(std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->cx) && std::isfinite(c->cy)) || c->fx == 0.0f || c->fy == 0.0f)
-        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: intrinsics must be finite with fx, fy != 0");
-    *n_obj = (int)total;
+        return fail(VMAPSTEP_ERR_ARGUMENT, "%s: intrinsics must be finite with fx, fy != 0", name);
     return VMAPSTEP_OK;
 }
 
-static int check_scene_workspace(const vl::SceneLayout& l, void* workspace, size_t workspace_bytes) {
+static vl::SceneLayout view_layout_of(const ViewCall& v, vl::SceneGroup* g) {
+    for (int i = 0; i < v.n_groups; ++i) g[i] = vl::SceneGroup{v.groups[i].hidden, v.groups[i].n_obj, v.groups[i].samples};
+    return vl::scene_layout(g, v.n_groups, v.cfg->pix_begin, v.cfg->pix_end, v.plan_cap);
+}
+
+static int check_view_workspace(const ViewCall& v, const vl::SceneLayout& l, void* workspace, size_t workspace_bytes) {
     if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < l.bytes)
-        return fail(VMAPSTEP_ERR_WORKSPACE, "scene view workspace must be 256-byte aligned and >= %zu bytes", l.bytes);
+        return fail(VMAPSTEP_ERR_WORKSPACE, "%s workspace must be 256-byte aligned and >= %zu bytes", v.name, l.bytes);
     return VMAPSTEP_OK;
 }
 
-static vv::ViewArgs scene_args(const vmapstep_view_cfg* c, const vl::SceneGroup* g, int n_groups, const vl::SceneLayout& l, const float* boxes,
-                               void* workspace) {
+static vv::ViewArgs view_args(const ViewCall& v, const vl::SceneGroup* g, const vl::SceneLayout& l, const float* boxes, void* workspace) {
+    const vmapstep_view_cfg* c = v.cfg;
     vv::ViewArgs a;
     std::memset(&a, 0, sizeof(a));
     a.cam.fx = c->fx; a.cam.fy = c->fy; a.cam.cx = c->cx; a.cam.cy = c->cy;
     std::memcpy(a.cam.T, c->t_wc, sizeof(a.cam.T));
-    a.cam.min_depth = c->min_depth; a.cam.width = c->width; a.cam.height = c->height; a.cam.samples = 0;
+    a.cam.min_depth = c->min_depth; a.cam.width = c->width; a.cam.height = c->height;
+    a.cam.samples = v.n_groups == 1 ? g[0].samples : 0;                    // view_composite<false>; the field launches set their own
     a.n_obj = l.n_obj; a.pix_begin = c->pix_begin; a.pix_end = c->pix_end; a.nb = vl::view_blocks(c->pix_begin, c->pix_end);
     a.boxes = boxes;
     char* ws = static_cast<char*>(workspace);
     a.wimg = ws;
     a.blk = reinterpret_cast<long long*>(ws + l.off_blk);
     a.plan = reinterpret_cast<int*>(ws + l.off_plan);
+    a.plan_cap = l.plan_cap;
     int end = 0;
     for (int i = 0; i < vv::kViewMaxGroups; ++i) {
-        if (i < n_groups) end += g[i].n_obj;
+        if (i < v.n_groups) end += g[i].n_obj;
         a.g_end[i] = end;
-        a.g_samples[i] = i < n_groups ? g[i].samples : 1;
+        a.g_samples[i] = i < v.n_groups ? g[i].samples : 1;
         a.g_per[i] = 1;
     }
     return a;
 }
 
-int vmapstep_scene_view_workspace_bytes(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, size_t* bytes) {
-    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+static int view_count_body(const ViewCall& v, const float* boxes, int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!boxes || !offsets) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: null argument", v.name);
     vl::SceneGroup g[vv::kViewMaxGroups];
-    int n_obj;
-    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
-    *bytes = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end).bytes;
-    return VMAPSTEP_OK;
-}
-
-int vmapstep_scene_view_count(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, const float* boxes,
-                              int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
-    vl::SceneGroup g[vv::kViewMaxGroups];
-    int n_obj;
-    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
-    if (!boxes || !offsets) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
-    const vl::SceneLayout l = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end);
-    if (int rc = check_scene_workspace(l, workspace, workspace_bytes)) return rc;
+    const vl::SceneLayout l = view_layout_of(v, g);
+    if (int rc = check_view_workspace(v, l, workspace, workspace_bytes)) return rc;
     VMAPSTEP_ON_STREAM_DEVICE(stream);
-    vv::ViewArgs a = scene_args(cfg, g, n_groups, l, boxes, workspace);
+    vv::ViewArgs a = view_args(v, g, l, boxes, workspace);
     a.offsets = reinterpret_cast<long long*>(offsets);
-    return vl::scene_view_count(a, static_cast<hipStream_t>(stream));
+    return vl::view_count(a, static_cast<hipStream_t>(stream));
 }
 
-int vmapstep_scene_view_render(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups,
-                               const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
-                               void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
-                               float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
-                               void* workspace, size_t workspace_bytes, void* stream) {
+static int view_render_body(const ViewCall& v, const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                            void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                            float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                            void* workspace, size_t workspace_bytes, void* stream) {
     vl::SceneGroup g[vv::kViewMaxGroups];
-    int n_obj;
-    if (int rc = check_scene(cfg, groups, n_groups, g, &n_obj)) return rc;
-    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: n_pairs=%lld", (long long)n_pairs);
-    if (!offsets_host) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
-    if (offsets_host[0] != 0 || offsets_host[n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: offsets must run from 0 to n_pairs");
+    const vl::SceneLayout l = view_layout_of(v, g);
+    const int n_obj = l.n_obj;
+    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: n_pairs=%lld", v.name, (long long)n_pairs);
+    if (!offsets_host) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: null argument", v.name);
+    if (offsets_host[0] != 0 || offsets_host[n_obj] != n_pairs) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: offsets must run from 0 to n_pairs", v.name);
     for (int k = 0; k < n_obj; ++k)
-        if (offsets_host[k + 1] < offsets_host[k]) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: offsets decrease at object %d", k);
+        if (offsets_host[k + 1] < offsets_host[k]) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: offsets decrease at object %d", v.name, k);
     // every pair count is <= n_pairs < 2^63 / 64 only if n_pairs is sane: bound it before the products below
-    if (n_pairs >= (1ll << 31)) return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: samples of all groups < 2^31 (n_pairs=%lld): render the pixel range in bands", (long long)n_pairs);
-    const vl::ScenePlan plan = vl::scene_plan_host(reinterpret_cast<const long long*>(offsets_host), g, n_groups);
+    if (n_pairs >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "%s limits: samples of all groups < 2^31 (n_pairs=%lld): render the pixel range in bands", v.name, (long long)n_pairs);
+    const vl::ScenePlan plan = vl::scene_plan_host(reinterpret_cast<const long long*>(offsets_host), g, v.n_groups);
     if (plan.samples >= (1ll << 31))
-        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: samples of all groups < 2^31 (%lld): render the pixel range in bands", plan.samples);
-    for (int32_t i = 0; i < n_groups; ++i) {
-        if (int rc = check_params(groups[i].params, "params", false)) return rc;
-        if (!groups[i].pe_scale || !groups[i].pe_scale->ptr) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: pe_scale of group %d is null", (int)i);
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "%s limits: samples of all groups < 2^31 (%lld): render the pixel range in bands", v.name, plan.samples);
+    for (int i = 0; i < v.n_groups; ++i) {
+        if (int rc = check_params(v.groups[i].params, "params", false)) return rc;
+        if (!v.groups[i].pe_scale || !v.groups[i].pe_scale->ptr) return fail(VMAPSTEP_ERR_ARGUMENT, "%s: pe_scale of group %d is null", v.name, i);
     }
     if (!boxes || !centers || !offsets || !depth || !color || !opacity || !instance || !overflow ||
         (n_pairs > 0 && (!pairs || !sample_occ || !sample_rgb)))
-        return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: null argument");
-    const vl::SceneLayout l = vl::scene_layout(g, n_groups, cfg->pix_begin, cfg->pix_end);
-    if (int rc = check_scene_workspace(l, workspace, workspace_bytes)) return rc;
+        return fail(VMAPSTEP_ERR_ARGUMENT, "%s: null argument", v.name);
+    if (int rc = check_view_workspace(v, l, workspace, workspace_bytes)) return rc;
     VMAPSTEP_ON_STREAM_DEVICE(stream);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    vv::ViewArgs a = scene_args(cfg, g, n_groups, l, boxes, workspace);
+    vv::ViewArgs a = view_args(v, g, l, boxes, workspace);
     a.centers = centers;
     a.offsets = const_cast<long long*>(reinterpret_cast<const long long*>(offsets));
     a.pairs = static_cast<vg::Pair*>(pairs); a.cap = n_pairs;
     a.occ = sample_occ; a.rgb = sample_rgb;
     a.depth = depth; a.color = color; a.opacity = opacity; a.instance = instance; a.overflow = overflow;
-    for (int i = 0; i < n_groups; ++i) { a.g_shift[i] = plan.shift[i]; a.g_per[i] = plan.per[i]; }
-    if (int rc = vl::scene_view_emit(a, st)) return rc;
+    for (int i = 0; i < v.n_groups; ++i) { a.g_shift[i] = plan.shift[i]; a.g_per[i] = plan.per[i]; }
+    if (int rc = vl::view_emit(a, st)) return rc;
     // the field pass, group by group.  Each launch gets the GROUP's argument block: its objects alone (object index, centres, scales,
     // offsets and images start at the group's first object), its sample count as cam.samples, its plan entries, and occ / rgb placed so
     // that pair * samples addresses the group's section (integer arithmetic: the address of element g_shift of the buffers)
     int k0 = 0;
-    for (int i = 0; i < n_groups; ++i) {
-        const vmapstep_view_group& q = groups[i];
+    for (int i = 0; i < v.n_groups; ++i) {
+        const vmapstep_view_group& q = v.groups[i];
         vv::ViewArgs b = a;
         b.n_obj = q.n_obj; b.cam.samples = q.samples;
         b.centers = centers + 3 * k0; b.offsets = a.offsets + k0;
@@ -1024,10 +917,106 @@ int vmapstep_scene_view_render(const vmapstep_view_cfg* cfg, const vmapstep_view
         for (int t = 0; t < VMAPSTEP_NUM_FC; ++t) pk.fc[t] = {q.params->fc[t].ptr, q.params->fc[t].obj_stride};
         pk.pe_B = {q.params->pe_B.ptr, q.params->pe_B.obj_stride};
         pk.wimg = reinterpret_cast<float*>(const_cast<char*>(b.wimg));
-        if (int rc = vl::scene_field(pk, b, plan.entries[i], st)) return rc;
+        if (int rc = vl::view_field(pk, b, plan.entries[i], st)) return rc;
         k0 += q.n_obj;
     }
-    return vl::scene_view_composite(a, st);
+    return vl::view_composite(a, st);
+}
+
+// ---- the single-group hidden-32 entry points: cfg->n_obj objects with cfg->samples samples per hit --------------------------------------
+static int check_view_cfg(const vmapstep_view_cfg* c) {
+    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "view: cfg is null");
+    if (c->samples < 1 || c->samples > vv::kViewMaxSamples || c->n_obj < 1 || c->n_obj > vv::kViewMaxObj || c->width < 1 || c->height < 1 ||
+        c->width > 16384 || c->height > 16384)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: 1 <= samples <= %d, 1 <= n_obj <= %d, 1 <= width, height <= 16384 (samples=%d n_obj=%d width=%d height=%d)",
+                    vv::kViewMaxSamples, vv::kViewMaxObj, c->samples, c->n_obj, c->width, c->height);
+    return check_camera("view", c);
+}
+
+static ViewCall one_group(const vmapstep_view_cfg* c, vmapstep_view_group* group, const vmapstep_params* params, const vmapstep_tensor* pe_scale) {
+    *group = vmapstep_view_group{32, c->n_obj, c->samples, 0, params, pe_scale};
+    return ViewCall{"view", c, group, 1, kViewFrontPlanCap};
+}
+
+int vmapstep_view_workspace_bytes(const vmapstep_view_cfg* cfg, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_view_cfg(cfg)) return rc;
+    vmapstep_view_group group;
+    vl::SceneGroup g[vv::kViewMaxGroups];
+    *bytes = view_layout_of(one_group(cfg, &group, nullptr, nullptr), g).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_view_count(const vmapstep_view_cfg* cfg, const float* boxes, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (int rc = check_view_cfg(cfg)) return rc;
+    vmapstep_view_group group;
+    return view_count_body(one_group(cfg, &group, nullptr, nullptr), boxes, offsets, workspace, workspace_bytes, stream);
+}
+
+int vmapstep_view_render(const vmapstep_view_cfg* cfg, int32_t hidden, const vmapstep_params* params, const vmapstep_tensor* pe_scale,
+                         const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                         void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                         float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (hidden != 32) return fail(VMAPSTEP_ERR_UNSUPPORTED, "view: hidden=%d, the view renderer implements hidden 32 only", hidden);
+    if (int rc = check_view_cfg(cfg)) return rc;
+    // these fire before the offsets are looked at, the shared body's come after: the order of this entry point's checks stays
+    if (n_pairs < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "view: n_pairs=%lld", (long long)n_pairs);
+    if (n_pairs * cfg->samples >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "view limits: n_pairs * samples < 2^31 (n_pairs=%lld samples=%d): render the pixel range in bands",
+                    (long long)n_pairs, cfg->samples);
+    if (int rc = check_params(params, "params", false)) return rc;
+    if (!pe_scale || !pe_scale->ptr || !boxes || !centers || !offsets || !offsets_host || !depth || !color || !opacity || !instance || !overflow ||
+        (n_pairs > 0 && (!pairs || !sample_occ || !sample_rgb)))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "view: null argument");
+    vmapstep_view_group group;
+    return view_render_body(one_group(cfg, &group, params, pe_scale), boxes, centers, offsets, offsets_host, pairs, n_pairs, sample_occ, sample_rgb,
+                            depth, color, opacity, instance, overflow, workspace, workspace_bytes, stream);
+}
+
+// ---- the scene entry points: 1 .. VMAPSTEP_VIEW_MAX_GROUPS groups ------------------------------------------------------------------------
+static int check_scene(const vmapstep_view_cfg* c, const vmapstep_view_group* groups, int32_t n_groups) {
+    if (!c) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: cfg is null");
+    if (n_groups < 1 || n_groups > vv::kViewMaxGroups)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: 1 <= n_groups <= %d (n_groups=%d)", vv::kViewMaxGroups, n_groups);
+    if (!groups) return fail(VMAPSTEP_ERR_ARGUMENT, "scene view: groups is null");
+    long long total = 0;
+    for (int32_t i = 0; i < n_groups; ++i) {
+        const vmapstep_view_group& q = groups[i];
+        if (q.hidden < 32 || q.hidden > 256 || q.hidden % 32 != 0 || q.samples < 1 || q.samples > vv::kViewMaxSamples || q.n_obj < 1)
+            return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: hidden a multiple of 32 in [32, 256], 1 <= samples <= %d, n_obj >= 1 "
+                        "(group %d: hidden=%d samples=%d n_obj=%d)", vv::kViewMaxSamples, (int)i, q.hidden, q.samples, q.n_obj);
+        total += q.n_obj;
+    }
+    if (total > vv::kViewMaxObj || c->width < 1 || c->height < 1 || c->width > 16384 || c->height > 16384)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "scene view limits: objects of all groups <= %d, 1 <= width, height <= 16384 (objects=%lld width=%d height=%d)",
+                    vv::kViewMaxObj, total, c->width, c->height);
+    return check_camera("scene view", c);
+}
+
+int vmapstep_scene_view_workspace_bytes(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_scene(cfg, groups, n_groups)) return rc;
+    vl::SceneGroup g[vv::kViewMaxGroups];
+    *bytes = view_layout_of(ViewCall{"scene view", cfg, groups, n_groups, vl::kScenePlanCap}, g).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_scene_view_count(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups, const float* boxes,
+                              int64_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_scene(cfg, groups, n_groups)) return rc;
+    return view_count_body(ViewCall{"scene view", cfg, groups, n_groups, vl::kScenePlanCap}, boxes, offsets, workspace, workspace_bytes, stream);
+}
+
+int vmapstep_scene_view_render(const vmapstep_view_cfg* cfg, const vmapstep_view_group* groups, int32_t n_groups,
+                               const float* boxes, const float* centers, const int64_t* offsets, const int64_t* offsets_host,
+                               void* pairs, int64_t n_pairs, float* sample_occ, float* sample_rgb,
+                               float* depth, float* color, float* opacity, int32_t* instance, int32_t* overflow,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_scene(cfg, groups, n_groups)) return rc;
+    return view_render_body(ViewCall{"scene view", cfg, groups, n_groups, vl::kScenePlanCap}, boxes, centers, offsets, offsets_host, pairs, n_pairs,
+                            sample_occ, sample_rgb, depth, color, opacity, instance, overflow, workspace, workspace_bytes, stream);
 }
 
 // ---- frame ingest ------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """View rendering on the device: all object fields composited per pixel of a camera image (csrc/view_kernels.h, field_query_seg_s32
 of csrc/query_split_kernels.h, field_query_seg_gen of csrc/query_kernels.h; the contract is the view section of include/vmapstep.h).
 
-``render_view`` takes the stacked hidden-32 fields, one oriented box per object (``meshing.BoundingBox``, ``bounds.get_bounds`` -
+``render_view`` takes the stacked fields of one hidden width, one oriented box per object (``meshing.BoundingBox``, ``bounds.get_bounds`` -
 anything with ``.center``, ``.R`` with the axes as columns, ``.extent``), a camera-to-world pose and the intrinsics, and returns depth,
 colour, opacity and instance images in the width-major layout of every image here.  Per band of pixels: count the (object, pixel)
 hits, read their number (the one host synchronisation), allocate the pair and sample buffers, then one call that packs the parameter
@@ -11,8 +11,8 @@ the images are the same bits however the range is cut.  GPU only: there is no ea
 
 ``render_view_groups`` renders up to four ``FieldGroup`` s into ONE image: each group has its own hidden width (32, 64, ..., 256) and
 its own samples per hit - the object stack at hidden 32 with 16 samples plus the background model at hidden 128 in its room box with
-48 is the two-group case.  Objects are numbered through the groups in order (``View.instance``).  ``render_view`` with fields of
-another width than 32 is the one-group case of it.
+48 is the two-group case.  Objects are numbered through the groups in order (``View.instance``).  There is one path: ``render_view`` is
+the one-group call of it.
 """
 from __future__ import annotations
 
@@ -107,125 +107,38 @@ def _box_rows(boxes, n):
     return rows
 
 
-@torch.no_grad()
 def render_view(fields, boxes, t_wc, intrinsics, width, height, samples=16, min_depth=0.0, centers=None, pixel_range=None,
                 budget_bytes=256 << 20, return_samples=False) -> View:
-    """Render the objects ``fields`` inside their ``boxes`` from the camera-to-world pose ``t_wc`` ([4, 4]).
+    """Render the objects ``fields`` inside their ``boxes`` from the camera-to-world pose ``t_wc`` ([4, 4]): the one-group case of
+    ``render_view_groups``, at every hidden width.
 
     ``centers``: the field-frame centre of every object ([n, 3], the objects' ``obj_center``; default zeros).  ``pixel_range``:
     (begin, end) of the pixel index w * height + h to render (default the whole image; the other pixels stay 0 / -1).
     ``budget_bytes``: the sample buffers of one call; a range that needs more is rendered in bands.  ``return_samples``: also return the
-    pair records, offsets and per-sample occupancy / colour - of ONE call, so the budget is not applied."""
-    fc, pe_B, scale = stack_fields(fields)
-    n = int(pe_B.shape[0])
-    dev = pe_B.device
-    if dev.type != "cuda":
-        raise _lib.VmapStepError("render_view runs on the GPU (no CPU fallback)")
-    if len(fc) != _lib.NUM_FC or int(fc[0].shape[1]) not in WIDTHS:
-        raise _lib.VmapStepError("render_view: hidden widths 32, 64, ..., 256 only")
-    if fc[0].shape[1] != 32:                   # the wide field kernel: the one-group case of render_view_groups
-        v = render_view_groups([FieldGroup((fc, pe_B, scale), boxes, centers, samples)], t_wc, intrinsics, width, height, min_depth=min_depth,
-                               pixel_range=pixel_range, budget_bytes=budget_bytes, return_samples=return_samples)
-        if v.group_pairs is not None:
-            v.sample_occ, v.sample_rgb = v.group_sample_occ[0], v.group_sample_rgb[0]
-        return v
-    width, height, samples = int(width), int(height), int(samples)
-    lib = _lib.load()
-    pp = _lib.Params()
-    for t, p in enumerate(list(fc) + [pe_B]):
-        if p.dtype != torch.float32 or p.device != dev or p.shape[0] != n or not p[0].is_contiguous():
-            raise _lib.VmapStepError("render_view: field parameters must be float32, on one device, stacked over the objects and contiguous per object")
-        ref = _lib.Tensor(p.data_ptr(), p.stride(0))
-        if t < _lib.NUM_FC:
-            pp.fc[t] = ref
-        else:
-            pp.pe_B = ref
-    scale = scale.to(dev, torch.float32).reshape(n).contiguous()
-    sc = _lib.Tensor(scale.data_ptr(), 1)
-    boxes_d = torch.from_numpy(_box_rows(list(boxes), n)).to(dev)
-    if centers is None:
-        centers_d = torch.zeros(n, 3, dtype=torch.float32, device=dev)
-    else:
-        centers_d = torch.as_tensor(np.asarray([[float(v) for v in (c if c is not None else (0, 0, 0))] for c in centers], np.float32)
-                                    if not torch.is_tensor(centers) else centers).to(dev, torch.float32).reshape(n, 3).contiguous()
-    T = (t_wc.detach().cpu().numpy() if torch.is_tensor(t_wc) else np.asarray(t_wc)).astype(np.float32).reshape(4, 4)
-    fx, fy, cx, cy = _intrinsics4(intrinsics)
-    npix = width * height
-    p0, p1 = (0, npix) if pixel_range is None else (int(pixel_range[0]), int(pixel_range[1]))
-
-    def cfg_of(b, e):
-        return _lib.ViewCfg(width, height, samples, n, fx, fy, cx, cy, (ctypes.c_float * 16)(*T.reshape(-1)), float(min_depth), b, e)
-
-    depth = torch.zeros(width, height, dtype=torch.float32, device=dev)
-    color = torch.zeros(width, height, 3, dtype=torch.float32, device=dev)
-    opacity = torch.zeros(width, height, dtype=torch.float32, device=dev)
-    instance = torch.full((width, height), -1, dtype=torch.int32, device=dev)
-    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-    offsets_d = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    total, bands, kept = 0, 0, None
-
-    def count(b, e):
-        cfg = cfg_of(b, e)
-        ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_view_workspace_bytes, dev, ctypes.byref(cfg))
-        _lib.check(lib.vmapstep_view_count(ctypes.byref(cfg), boxes_d.data_ptr(), offsets_d.data_ptr(), ws_ptr, nbytes, _devmem.stream(dev)), lib)
-        off_h = offsets_d.cpu().numpy().copy()           # the one host synchronisation of the band
-        return cfg, (ws, ws_ptr, nbytes), off_h
-
-    def band(b, e, counted=None):
-        nonlocal total, bands, kept
-        cfg, (ws, ws_ptr, nbytes), off_h = counted or count(b, e)
-        m = int(off_h[-1])
-        need = m * samples * BYTES_PER_SAMPLE
-        if not return_samples and need > budget_bytes and e - b > BLOCK:
-            parts = min(-(-need // max(int(budget_bytes), 1)), -(-(e - b) // BLOCK))
-            step = -(-(e - b) // parts)
-            step = -(-step // BLOCK) * BLOCK
-            cuts = list(range(b, e, step)) + [e]
-            if len(cuts) == 2:                           # cannot be cut on a block boundary any finer: halve
-                cuts = [b, b + max(BLOCK, (e - b) // 2 // BLOCK * BLOCK), e]
-            del ws
-            for i in range(len(cuts) - 1):
-                band(cuts[i], cuts[i + 1])
-            return
-        pairs = torch.empty(max(m, 1), 4, dtype=torch.int32, device=dev)
-        occ = torch.empty(max(m, 1), samples, dtype=torch.float32, device=dev)
-        rgb = torch.empty(max(m, 1), samples, 3, dtype=torch.float32, device=dev)
-        _lib.check(lib.vmapstep_view_render(ctypes.byref(cfg), 32, ctypes.byref(pp), ctypes.byref(sc), boxes_d.data_ptr(), centers_d.data_ptr(),
-                                            offsets_d.data_ptr(), off_h.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                            pairs.data_ptr(), m, occ.data_ptr(), rgb.data_ptr(),
-                                            depth.data_ptr(), color.data_ptr(), opacity.data_ptr(), instance.data_ptr(), overflow.data_ptr(),
-                                            ws_ptr, nbytes, _devmem.stream(dev)), lib)
-        total += m
-        bands += 1
-        if return_samples:
-            kept = (pairs[:m], off_h, occ[:m], rgb[:m])
-        # offsets_d is rewritten by the next band's count: same stream, so the order holds
-
-    with torch.cuda.device(dev):
-        if p1 > p0:
-            band(p0, p1)
-        ovf = int(overflow.item())
-    view = View(depth, color, opacity, instance, ovf, total, bands)
-    if return_samples and kept is not None:
-        view.pairs, view.offsets, view.sample_occ, view.sample_rgb = kept
-    return view
+    pair records, offsets and per-sample occupancy / colour - of ONE call, so the budget is not applied: ``View.sample_occ`` is
+    [n_pairs, S] and ``View.sample_rgb`` [n_pairs, S, 3], and the ``group_*`` lists hold the same one group."""
+    v = _render_groups("render_view", [FieldGroup(fields, boxes, centers, samples)], t_wc, intrinsics, width, height, min_depth, pixel_range,
+                       budget_bytes, return_samples)
+    if v.group_pairs is not None:
+        v.sample_occ, v.sample_rgb = v.group_sample_occ[0], v.group_sample_rgb[0]
+    return v
 
 
-def _prepare_group(g, dev):
-    """The C view of one FieldGroup: (ViewGroup fields, box rows, centres, keep-alive objects)."""
+def _prepare_group(name, g, dev):
+    """The C view of one FieldGroup: (ViewGroup fields, box rows, centres, keep-alive objects).  ``name``: the caller, for the messages."""
     fc, pe_B, scale = stack_fields(g.fields)
     n = int(pe_B.shape[0])
     if dev is not None and pe_B.device != dev:
-        raise _lib.VmapStepError("render_view_groups: all groups must be on one device")
+        raise _lib.VmapStepError(f"{name}: all groups must be on one device")
     dev = pe_B.device
     if dev.type != "cuda":
-        raise _lib.VmapStepError("render_view_groups runs on the GPU (no CPU fallback)")
+        raise _lib.VmapStepError(f"{name} runs on the GPU (no CPU fallback)")
     if len(fc) != _lib.NUM_FC or int(fc[0].shape[1]) not in WIDTHS:
-        raise _lib.VmapStepError("render_view_groups: hidden widths 32, 64, ..., 256 only")
+        raise _lib.VmapStepError(f"{name}: hidden widths 32, 64, ..., 256 only")
     pp = _lib.Params()
     for t, p in enumerate(list(fc) + [pe_B]):
         if p.dtype != torch.float32 or p.device != dev or p.shape[0] != n or not p[0].is_contiguous():
-            raise _lib.VmapStepError("render_view_groups: field parameters must be float32, on one device, stacked over the objects and contiguous per object")
+            raise _lib.VmapStepError(f"{name}: field parameters must be float32, on one device, stacked over the objects and contiguous per object")
         ref = _lib.Tensor(p.data_ptr(), p.stride(0))
         if t < _lib.NUM_FC:
             pp.fc[t] = ref
@@ -250,12 +163,17 @@ def render_view_groups(groups, t_wc, intrinsics, width, height, min_depth=0.0, p
     fields are sampled inside their boxes with the group's own sample count and all samples of a pixel are merged as ``render_view``
     merges them.  ``View.instance`` numbers the objects through the groups in order.  The other arguments are ``render_view``'s; a
     band's bytes sum over the groups' own sample counts."""
+    return _render_groups("render_view_groups", groups, t_wc, intrinsics, width, height, min_depth, pixel_range, budget_bytes, return_samples)
+
+
+@torch.no_grad()
+def _render_groups(name, groups, t_wc, intrinsics, width, height, min_depth, pixel_range, budget_bytes, return_samples):
     groups = list(groups)
     if not 1 <= len(groups) <= MAX_GROUPS:
-        raise _lib.VmapStepError(f"render_view_groups: 1 .. {MAX_GROUPS} groups ({len(groups)} given)")
+        raise _lib.VmapStepError(f"{name}: 1 .. {MAX_GROUPS} groups ({len(groups)} given)")
     dev, G = None, []
     for g in groups:
-        d, dev = _prepare_group(g, dev)
+        d, dev = _prepare_group(name, g, dev)
         G.append(d)
     ng = len(G)
     n = sum(d["n"] for d in G)
