@@ -652,6 +652,60 @@ int vmapstep_filter_write(const vmapstep_filter_cfg* cfg, const void* depth, con
 int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* offsets, int32_t n_seg, float voxel_size,
                           float* points, float* bounds, void* stream);
 
+/* ---- visibility culling: what the keyframes saw of a cloud, and a mesh compacted by such a mask ---------------------------------------
+ * Scene-level evaluation first removes, from the reconstruction and from the ground truth, what no frame observed.  The reference
+ * leaves that to outside tools; the contract below is this project's own (csrc/cull_rules.h is the definition).
+ *
+ * Frames: depth (DEVICE float32 [slots][width][height], width-major as in a FrameStore) and t_wc (DEVICE float32 [slots][4][4],
+ * camera to world, row-major; T below = its first 12 floats, the rotation ASSUMED orthonormal).  Frame k of the call reads slot
+ * slots[k] (DEVICE int32 [n_frames]) of both, or slot k when slots is NULL; every slot must exist - the library cannot check device
+ * values.  The offset into depth is 64-bit.
+ *
+ * A point p (points: DEVICE float32 [n_points][3]) is seen by a frame iff, in float32 with every fma ONE fused operation, every other
+ * operation rounded on its own and IEEE division:
+ *   q = p - t;  c_i = fma(T[8 + i], q2, fma(T[4 + i], q1, T[i] * q0)) for i = 0, 1, 2 (R^T q);  z = c_2 and z > min_depth;
+ *   u = fma(fx, c_0 / z, cx), v = fma(fy, c_1 / z, cy);  w = rintf(u), h = rintf(v), half to even;
+ *   margin <= w <= width - 1 - margin and margin <= h <= height - 1 - margin, compared as floats; a NaN anywhere fails;
+ *   and, when cfg.use_depth: d = depth[slot][w][h], d > 0 and z <= d + occlusion_eps (one rounded add).
+ * Without use_depth the depth images are not read and `depth` may be NULL.  A point is seen iff any frame sees it: a set, exact and
+ * independent of order.  An all-zero pose (an unused slot) sees nothing.
+ *
+ * vmapstep_cull_mark: `seen` (DEVICE uint8 [n_points]) is read and written: a point whose byte is non-zero is not tested, and the call
+ * only ever turns a 0 into a 1 (nothing else is written), so frames marked in chunks across calls give the result of one call.
+ * n_frames == 0 or n_points == 0 is VMAPSTEP_OK and writes nothing.
+ *
+ * vmapstep_cull_faces_count / _emit: the compaction of faces (DEVICE int32 [n_faces][3]) by `seen` (DEVICE uint8 [n_vertices]).  A face
+ * is kept iff at least min_seen (1, 2 or 3) of its corners are seen - a repeated index counts once per corner; a vertex is kept iff a
+ * kept face references it (with min_seen < 3 that includes unseen corners).  _count writes counts (DEVICE int64 [2]) = {kept faces,
+ * kept vertices}; the caller reads them, allocates and calls _emit with the same faces, seen, min_seen and workspace: kept_vertices
+ * (DEVICE int32 [n_kept_vertices]) receives the old index of every new vertex in ascending order, faces_out (DEVICE int32
+ * [n_kept_faces][3]) the kept faces in the input's order, re-indexed; nothing is written at or past the two counts.  Face indices are
+ * DEVICE values: like the other mesh entry points (vmapstep_clip_box_*, vmapstep_surface_sample) the library does not check them on
+ * the host; the kernels never follow an index outside [0, n_vertices), and a face that holds one is dropped.
+ * Workspace: 256-byte aligned, >= vmapstep_cull_workspace_bytes(n_vertices, n_faces) (VMAPSTEP_ERR_WORKSPACE otherwise).
+ *
+ * Everything is enqueued on `stream`, nothing waits.  VMAPSTEP_ERR_ARGUMENT before anything is enqueued: a null pointer; width or
+ * height < 1; margin < 0 or 2 * margin >= width or height (no pixel left); min_depth negative or not finite; fx, fy, cx, cy not finite
+ * or fx, fy zero; use_depth with a NULL depth or an occlusion_eps that is negative or NaN; min_seen outside 1..3; a count that is
+ * negative or >= 2^31; faces without vertices. */
+typedef struct vmapstep_cull_cfg {
+    float fx, fy, cx, cy;
+    float min_depth;               /* >= 0 */
+    float occlusion_eps;           /* metres; read only when use_depth */
+    int32_t width, height;
+    int32_t margin;                /* pixels at the border that do not count */
+    int32_t use_depth;             /* 0: frustum only */
+} vmapstep_cull_cfg;
+
+int vmapstep_cull_mark(const float* points, int64_t n_points, const float* depth, const float* t_wc, const int32_t* slots, int32_t n_frames,
+                       const vmapstep_cull_cfg* cfg, uint8_t* seen, void* stream);
+int vmapstep_cull_workspace_bytes(int64_t n_vertices, int64_t n_faces, size_t* bytes);
+int vmapstep_cull_faces_count(const int32_t* faces, int64_t n_faces, const uint8_t* seen, int64_t n_vertices, int32_t min_seen,
+                              int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_cull_faces_emit(const int32_t* faces, int64_t n_faces, const uint8_t* seen, int64_t n_vertices, int32_t min_seen,
+                             int32_t* kept_vertices, int64_t n_kept_vertices, int32_t* faces_out, int64_t n_kept_faces,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -142,6 +142,14 @@ FILTER_BOX_FLOATS = 16                     # centre, three axes, three half exte
 FILTER_MAX_IDS = 32767
 FILTER_MAX_RADIUS = 8
 
+
+class CullCfg(ctypes.Structure):
+    """vmapstep_cull_cfg: the camera, the image size and the mode of one vmapstep_cull_mark call."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_depth", ctypes.c_float), ("occlusion_eps", ctypes.c_float),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("margin", ctypes.c_int32), ("use_depth", ctypes.c_int32)]
+
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -157,6 +165,7 @@ EXPORTS = (
     "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",
     "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame",
     "vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write", "vmapstep_voxel_points",
+    "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count", "vmapstep_cull_faces_emit",
 )
 
 _libs = {}
@@ -289,8 +298,17 @@ def load(path=None):
                                           ctypes.c_void_p, ctypes.c_void_p]
     lib.vmapstep_voxel_points.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_cull_mark.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                       ctypes.POINTER(CullCfg), ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_cull_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_cull_faces_count.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_cull_faces_emit.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
-               "vmapstep_voxel_points"):
+               "vmapstep_voxel_points", "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count",
+               "vmapstep_cull_faces_emit"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_unproject_workspace_bytes", "vmapstep_unproject_count", "vmapstep_unproject_emit", "vmapstep_obb_extents",
                "vmapstep_cloud_moments", "vmapstep_view_workspace_bytes", "vmapstep_view_count", "vmapstep_view_render",

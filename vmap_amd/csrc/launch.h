@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 namespace vk { struct WsArgs; }
 struct vmapstep_ingest_cfg;
 struct vmapstep_filter_cfg;
+struct vmapstep_cull_cfg;
 
 namespace vl {
 
@@ -125,5 +126,15 @@ int filter_write(const vmapstep_filter_cfg& cfg, const void* depth, const void* 
                  hipStream_t st);
 int voxel_points(const unsigned long long* keys, long long n_keys, const long long* offsets, int n_seg, float voxel, float* points, float* bounds,
                  hipStream_t st);
+
+// k_cull.hip: visibility culling (cull_kernels.h).  cull_mark only ever turns a 0 of `seen` into a 1.  The compaction's workspace is
+// vl::cull_layout's: cull_faces_count = cull_clear, cull_face_count, cull_vertex_count, cull_scan -> counts {kept faces, kept vertices};
+// cull_faces_emit = cull_vertex_emit, cull_face_emit on the workspace the count call left.
+int cull_mark(const vmapstep_cull_cfg& cfg, const float* points, long long n_points, const float* depth, const float* t_wc, const int* slots,
+              int n_frames, unsigned char* seen, hipStream_t st);
+int cull_faces_count(const int* faces, long long n_faces, const unsigned char* seen, long long n_vertices, int min_seen, long long* counts,
+                     void* workspace, hipStream_t st);
+int cull_faces_emit(const int* faces, long long n_faces, const unsigned char* seen, long long n_vertices, int min_seen, int* kept_vertices,
+                    long long n_kept_vertices, int* faces_out, long long n_kept_faces, void* workspace, hipStream_t st);
 
 }  // namespace vl

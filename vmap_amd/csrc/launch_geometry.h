@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest and filter families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter and cull families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -73,6 +73,15 @@ constexpr int kPixBlock = kFilterWG * kPixPer;
 constexpr int kMaxIds = 32767;
 constexpr int kMaxSide = 4095;
 }  // namespace vf
+
+namespace vc {
+constexpr int kCullWG = 256;               // every cull kernel but cull_scan; faces / vertices per block of the compaction
+constexpr int kPointsPer = 4;              // points per lane of cull_mark, kCullWG apart (a wave's 64 points are consecutive)
+constexpr int kCullTile = kCullWG * kPointsPer;   // points per workgroup of cull_mark
+constexpr int kFrameChunk = 32;            // frames whose poses one cull_mark workgroup stages in LDS at a time
+constexpr int kMaxChunkRows = 65535;       // grid rows of cull_mark (a row takes every kMaxChunkRows-th chunk beyond that)
+constexpr int kCullScanWG = 256;           // the single workgroup of cull_scan
+}  // namespace vc
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -275,6 +284,23 @@ inline FilterLayout filter_layout(int max_ids, int width, int height) {
     l.off_flags = l.off_table + ws_up((size_t)vf::kReplicas * max_ids * vf::kTableInts * sizeof(int));
     l.off_blk = l.off_flags + ws_up((size_t)width * height);
     l.bytes = l.off_blk + ws_up((size_t)filter_pix_blocks(width, height) * 2 * sizeof(int));
+    return l;
+}
+
+// Visibility culling, the compaction of a mesh by a vertex mask.  The workspace: one byte per vertex (referenced by a kept face),
+// the new index of every vertex (int32 [n_vertices], written by the emit call), and one int64 per block of vc::kCullWG faces and per
+// block of vc::kCullWG vertices (the block's kept count, then - after cull_scan - its exclusive prefix).
+struct CullLayout {
+    int nfb, nvb; size_t off_newidx, off_fblk, off_vblk, bytes;
+};
+inline CullLayout cull_layout(long long n_vertices, long long n_faces) {
+    CullLayout l;
+    l.nfb = (int)ceil_div(n_faces, vc::kCullWG);
+    l.nvb = (int)ceil_div(n_vertices, vc::kCullWG);
+    l.off_newidx = ws_up((size_t)n_vertices);
+    l.off_fblk = l.off_newidx + ws_up((size_t)n_vertices * sizeof(int));
+    l.off_vblk = l.off_fblk + ws_up((size_t)l.nfb * sizeof(long long)) + 256;
+    l.bytes = l.off_vblk + ws_up((size_t)l.nvb * sizeof(long long)) + 256;
     return l;
 }
 

@@ -1127,6 +1127,70 @@ int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* o
                             voxel_size, points, bounds, static_cast<hipStream_t>(stream));
 }
 
+// ---- visibility culling ------------------------------------------------------------------------------------------------------------
+static int check_cull_cfg(const vmapstep_cull_cfg* cfg, const float* depth) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: cfg is null");
+    if (cfg->width < 1 || cfg->height < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: width=%d height=%d", cfg->width, cfg->height);
+    if (cfg->margin < 0 || 2ll * cfg->margin >= cfg->width || 2ll * cfg->margin >= cfg->height)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "cull: margin=%d leaves no pixel of %d x %d", cfg->margin, cfg->width, cfg->height);
+    if (!(cfg->min_depth >= 0.0f) || !std::isfinite(cfg->min_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: min_depth must be finite and >= 0");
+    if (!std::isfinite(cfg->fx) || !std::isfinite(cfg->fy) || !std::isfinite(cfg->cx) || !std::isfinite(cfg->cy) || cfg->fx == 0.0f || cfg->fy == 0.0f)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "cull: intrinsics must be finite with fx, fy != 0");
+    if (cfg->use_depth && !depth) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: use_depth with a null depth");
+    if (cfg->use_depth && !(cfg->occlusion_eps >= 0.0f)) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: occlusion_eps must be a number >= 0");
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_cull_mark(const float* points, int64_t n_points, const float* depth, const float* t_wc, const int32_t* slots, int32_t n_frames,
+                       const vmapstep_cull_cfg* cfg, uint8_t* seen, void* stream) {
+    if (int rc = check_cull_cfg(cfg, depth)) return rc;
+    if (n_points < 0 || n_points >= (1ll << 31) || n_frames < 0)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "cull_mark: n_points=%lld n_frames=%d", (long long)n_points, n_frames);
+    if (n_points == 0 || n_frames == 0) return VMAPSTEP_OK;
+    if (!points || !t_wc || !seen) return fail(VMAPSTEP_ERR_ARGUMENT, "cull_mark: null argument");
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::cull_mark(*cfg, points, n_points, depth, t_wc, reinterpret_cast<const int*>(slots), n_frames, seen, static_cast<hipStream_t>(stream));
+}
+
+static int check_cull_faces(const int32_t* faces, int64_t n_faces, const uint8_t* seen, int64_t n_vertices, int32_t min_seen) {
+    if (n_vertices < 0 || n_vertices >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: counts 0 .. 2^31 - 1");
+    if (min_seen < 1 || min_seen > 3) return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: min_seen=%d outside 1..3", min_seen);
+    if (n_faces > 0 && n_vertices == 0) return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: %lld faces and no vertex", (long long)n_faces);
+    if (n_faces > 0 && (!faces || !seen)) return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: null argument");
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_cull_workspace_bytes(int64_t n_vertices, int64_t n_faces, size_t* bytes) {
+    if (!bytes || n_vertices < 0 || n_vertices >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "null / negative argument");
+    *bytes = vl::cull_layout(n_vertices, n_faces).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_cull_faces_count(const int32_t* faces, int64_t n_faces, const uint8_t* seen, int64_t n_vertices, int32_t min_seen,
+                              int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_cull_faces(faces, n_faces, seen, n_vertices, min_seen)) return rc;
+    if (!counts) return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::cull_layout(n_vertices, n_faces).bytes, "cull")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::cull_faces_count(reinterpret_cast<const int*>(faces), n_faces, seen, n_vertices, min_seen, reinterpret_cast<long long*>(counts),
+                                workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_cull_faces_emit(const int32_t* faces, int64_t n_faces, const uint8_t* seen, int64_t n_vertices, int32_t min_seen,
+                             int32_t* kept_vertices, int64_t n_kept_vertices, int32_t* faces_out, int64_t n_kept_faces,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_cull_faces(faces, n_faces, seen, n_vertices, min_seen)) return rc;
+    if (n_kept_vertices < 0 || n_kept_faces < 0 || (n_kept_vertices > 0 && !kept_vertices) || (n_kept_faces > 0 && !faces_out))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "cull faces: null argument / negative count");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::cull_layout(n_vertices, n_faces).bytes, "cull")) return rc;
+    if (n_faces == 0 || n_kept_faces == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::cull_faces_emit(reinterpret_cast<const int*>(faces), n_faces, seen, n_vertices, min_seen, reinterpret_cast<int*>(kept_vertices),
+                               n_kept_vertices, reinterpret_cast<int*>(faces_out), n_kept_faces, workspace, static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

@@ -256,13 +256,27 @@ def main(argv=None):
     ap.add_argument("gt")
     ap.add_argument("--n", type=int, default=200000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--frames", metavar="FILE.npz", default=None,
+                    help="depth [K,W,H], t_wc [K,4,4] and intrinsics [4]: both meshes are culled to what these frames saw first")
+    ap.add_argument("--occlusion-eps", type=float, default=None, metavar="X",
+                    help="with --frames: the occlusion tolerance in metres (default: the frustum test alone)")
     args = ap.parse_args(argv)
-    m = calc_3d_metric(load_mesh(args.rec), load_mesh(args.gt), N=args.n, seed=args.seed)
+    rec, gt = load_mesh(args.rec), load_mesh(args.gt)
+    if args.frames is None and args.occlusion_eps is not None:
+        ap.error("--occlusion-eps needs --frames")
+    if args.frames is not None:
+        from . import visibility
+        with np.load(args.frames) as fr:
+            depth, t_wc, intrinsics = fr["depth"], fr["t_wc"], fr["intrinsics"]
+        rec, gt = (None if m is None else visibility.cull_to_views(m, depth, t_wc, intrinsics, args.occlusion_eps) for m in (rec, gt))
+    m = None if rec is None or gt is None else calc_3d_metric(rec, gt, N=args.n, seed=args.seed)
     if m is None:
         print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None}))
         return 1
+    culled = {} if args.frames is None else {"frames": args.frames, "occlusion_eps": args.occlusion_eps, "rec_faces": len(rec.faces),
+                                             "gt_faces": len(gt.faces)}
     print(json.dumps({"rec": args.rec, "gt": args.gt, "n": args.n, "seed": args.seed, "accuracy": m[0][0], "completion": m[1][0],
-                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0]}))
+                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0], **culled}))
     return 0
 
 
