@@ -706,6 +706,44 @@ int vmapstep_cull_faces_emit(const int32_t* faces, int64_t n_faces, const uint8_
                              int32_t* kept_vertices, int64_t n_kept_vertices, int32_t* faces_out, int64_t n_kept_faces,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh components: label, measure and drop floaters ---------------------------------------------------------------------------------
+ * A field queried over its whole box yields the object's surface plus floaters: small closed blobs where the occupancy crosses 0.5
+ * in space nobody constrained.  The contract below is this project's own (csrc/component_rules.h is the definition); its labels are
+ * what scipy.sparse.csgraph.connected_components gives on the edge graph.
+ *
+ * Connectivity.  faces: DEVICE int32 [n_faces][3] over n_vertices vertices.  Two vertices are connected iff a chain of faces links
+ * them - by shared vertex INDICES, not by position, and one shared vertex is enough (vertex connectivity: coarser than an edge
+ * adjacency where two sheets touch in a single vertex).  A face with an index outside [0, n_vertices) is ignored whole: it connects
+ * nothing and counts nowhere, and no kernel follows such an index.  A face with a repeated index still connects its distinct corners
+ * and still counts as a face.  A vertex no valid face references is a component of its own: one vertex, no face.
+ *
+ * Labels.  labels: DEVICE int32 [n_vertices].  Components are numbered densely 0 .. C - 1 in ascending order of their smallest
+ * vertex index; counts (DEVICE int64 [1]) receives C.  The result depends on nothing but the input - not on schedule, launch shape
+ * or run: the union always links the larger root under the smaller, so a component's root is its smallest vertex whatever the order
+ * of arrival, and the numbering is an integer scan over the roots.
+ *
+ * Statistics, per component: comp_vertices (DEVICE int32 [n_components]), comp_faces and comp_area_q (DEVICE int64 [n_components]),
+ * all three zeroed by the call.  A valid face belongs to the component of its corners.  Its area, in float32 with NO fused operation,
+ * every operation rounded on its own and an IEEE square root:
+ *   a = p1 - p0, b = p2 - p0;  c = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0);  area = 0.5 * sqrt((c0 c0 + c1 c1) + c2 c2)
+ * then in units of 2^-40 m^2: rint((double)area * 2^40), half to even; NaN, an infinity, zero or a negative value count 0; one face is
+ * clamped at 2^62 units.  comp_area_q is the integer sum of these (wrapping like int64; it holds 8e6 m^2): exact, independent of
+ * order, comparable bit for bit - which a float sum by atomics would not be, and a keep / drop decision made on it is reproducible.
+ * With vertices == NULL the areas stay 0.  A label outside [0, n_components) is not counted (labels are device values).
+ *
+ * Selection (vmap_amd/components.py; kr::component_kept): a component is kept iff comp_faces >= min_faces, comp_area_q >=
+ * rint(min_area * 2^40) and, where largest = k is given, it is among the k largest by comp_area_q, ties to the lower number.
+ *
+ * Everything is enqueued on `stream`, nothing waits.  n_vertices == 0 is VMAPSTEP_OK with C = 0.  VMAPSTEP_ERR_ARGUMENT before
+ * anything is enqueued: a null pointer that would be read or written; a negative size; n_vertices or n_faces >= 2^31; n_components
+ * outside [0, n_vertices].  Workspace: 256-byte aligned, >= vmapstep_components_workspace_bytes(n_vertices, n_faces)
+ * (VMAPSTEP_ERR_WORKSPACE otherwise). */
+int vmapstep_components_workspace_bytes(int64_t n_vertices, int64_t n_faces, size_t* bytes);
+int vmapstep_components_label(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* labels, int64_t* counts, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int vmapstep_components_stats(const float* vertices, const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_vertices,
+                              int64_t n_components, int32_t* comp_vertices, int64_t* comp_faces, int64_t* comp_area_q, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip, k_components.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -136,5 +136,12 @@ int cull_faces_count(const int* faces, long long n_faces, const unsigned char* s
                      void* workspace, hipStream_t st);
 int cull_faces_emit(const int* faces, long long n_faces, const unsigned char* seen, long long n_vertices, int min_seen, int* kept_vertices,
                     long long n_kept_vertices, int* faces_out, long long n_kept_faces, void* workspace, hipStream_t st);
+
+// k_components.hip: mesh components (component_kernels.h).  components_label = comp_init, comp_hook, comp_flatten, comp_scan ->
+// counts {C}, comp_root_emit, comp_relabel on the workspace of vl::component_layout; components_stats zeroes the three outputs
+// (memsets on the stream), then comp_face_stats and comp_vertex_stats.
+int components_label(const int* faces, long long n_faces, long long n_vertices, int* labels, long long* counts, void* workspace, hipStream_t st);
+int components_stats(const float* vertices, const int* faces, long long n_faces, const int* labels, long long n_vertices, long long n_components,
+                     int* comp_vertices, long long* comp_faces, long long* comp_area_q, hipStream_t st);
 
 }  // namespace vl

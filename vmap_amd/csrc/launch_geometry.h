@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter and cull families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, cull and component families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h, component_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -82,6 +82,13 @@ constexpr int kFrameChunk = 32;            // frames whose poses one cull_mark w
 constexpr int kMaxChunkRows = 65535;       // grid rows of cull_mark (a row takes every kMaxChunkRows-th chunk beyond that)
 constexpr int kCullScanWG = 256;           // the single workgroup of cull_scan
 }  // namespace vc
+
+namespace vcc {
+constexpr int kCompWG = 256;               // comp_init / _hook / _flatten / _root_emit / _relabel; vertices per block of the root numbering
+constexpr int kCompScanWG = 256;           // the single workgroup of comp_scan
+constexpr int kStatsWG = 1024;             // comp_face_stats / comp_vertex_stats: sixteen waves share one LDS table before the global atomics
+constexpr int kStatsSlots = 64;            // rows of that table, keyed by component % kStatsSlots (a second component on a row goes straight to memory)
+}  // namespace vcc
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -300,6 +307,22 @@ inline CullLayout cull_layout(long long n_vertices, long long n_faces) {
     l.off_newidx = ws_up((size_t)n_vertices);
     l.off_fblk = l.off_newidx + ws_up((size_t)n_vertices * sizeof(int));
     l.off_vblk = l.off_fblk + ws_up((size_t)l.nfb * sizeof(long long)) + 256;
+    l.bytes = l.off_vblk + ws_up((size_t)l.nvb * sizeof(long long)) + 256;
+    return l;
+}
+
+// Mesh components, the labelling.  The workspace: the union-find parents (int32 [n_vertices]), the dense number of every root
+// (int32 [n_vertices], read only at roots) and one int64 per block of vcc::kCompWG vertices (the block's roots, then - after
+// comp_scan - their exclusive prefix).  Faces need no workspace.
+struct ComponentLayout {
+    int nvb, nfb; size_t off_dense, off_vblk, bytes;
+};
+inline ComponentLayout component_layout(long long n_vertices, long long n_faces) {
+    ComponentLayout l;
+    l.nvb = (int)ceil_div(n_vertices, vcc::kCompWG);
+    l.nfb = (int)ceil_div(n_faces, vcc::kCompWG);
+    l.off_dense = ws_up((size_t)n_vertices * sizeof(int));
+    l.off_vblk = l.off_dense + ws_up((size_t)n_vertices * sizeof(int));
     l.bytes = l.off_vblk + ws_up((size_t)l.nvb * sizeof(long long)) + 256;
     return l;
 }

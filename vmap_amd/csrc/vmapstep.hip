@@ -1191,6 +1191,44 @@ int vmapstep_cull_faces_emit(const int32_t* faces, int64_t n_faces, const uint8_
                                n_kept_vertices, reinterpret_cast<int*>(faces_out), n_kept_faces, workspace, static_cast<hipStream_t>(stream));
 }
 
+// ---- mesh components ---------------------------------------------------------------------------------------------------------------
+static int check_component_sizes(int64_t n_vertices, int64_t n_faces) {
+    if (n_vertices < 0 || n_vertices >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "components: n_vertices=%lld n_faces=%lld outside 0 .. 2^31 - 1", (long long)n_vertices, (long long)n_faces);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_components_workspace_bytes(int64_t n_vertices, int64_t n_faces, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "components: null argument");
+    if (int rc = check_component_sizes(n_vertices, n_faces)) return rc;
+    *bytes = vl::component_layout(n_vertices, n_faces).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_components_label(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* labels, int64_t* counts, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (int rc = check_component_sizes(n_vertices, n_faces)) return rc;
+    if (!counts || (n_faces > 0 && !faces) || (n_vertices > 0 && !labels)) return fail(VMAPSTEP_ERR_ARGUMENT, "components_label: null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::component_layout(n_vertices, n_faces).bytes, "components")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::components_label(reinterpret_cast<const int*>(faces), n_faces, n_vertices, reinterpret_cast<int*>(labels),
+                                reinterpret_cast<long long*>(counts), workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_components_stats(const float* vertices, const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_vertices,
+                              int64_t n_components, int32_t* comp_vertices, int64_t* comp_faces, int64_t* comp_area_q, void* stream) {
+    if (int rc = check_component_sizes(n_vertices, n_faces)) return rc;
+    if (n_components < 0 || n_components > n_vertices)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "components_stats: n_components=%lld outside [0, n_vertices=%lld]", (long long)n_components, (long long)n_vertices);
+    if ((n_faces > 0 && !faces) || (n_vertices > 0 && !labels) || (n_components > 0 && (!comp_vertices || !comp_faces || !comp_area_q)))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "components_stats: null argument");
+    if (n_components == 0) return VMAPSTEP_OK;             // no row to write (n_vertices == 0 among them)
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::components_stats(vertices, reinterpret_cast<const int*>(faces), n_faces, reinterpret_cast<const int*>(labels), n_vertices, n_components,
+                                reinterpret_cast<int*>(comp_vertices), reinterpret_cast<long long*>(comp_faces),
+                                reinterpret_cast<long long*>(comp_area_q), static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

@@ -260,10 +260,20 @@ def main(argv=None):
                     help="depth [K,W,H], t_wc [K,4,4] and intrinsics [4]: both meshes are culled to what these frames saw first")
     ap.add_argument("--occlusion-eps", type=float, default=None, metavar="X",
                     help="with --frames: the occlusion tolerance in metres (default: the frustum test alone)")
+    ap.add_argument("--min-component-area", type=float, default=None, metavar="X",
+                    help="drop the components of REC (floaters) whose area is below X square metres, before any culling")
+    ap.add_argument("--largest-components", type=int, default=None, metavar="K", help="keep only the K largest components of REC by area")
     args = ap.parse_args(argv)
     rec, gt = load_mesh(args.rec), load_mesh(args.gt)
     if args.frames is None and args.occlusion_eps is not None:
         ap.error("--occlusion-eps needs --frames")
+    filtered = {}
+    if args.min_component_area is not None or args.largest_components is not None:
+        # REC only, and before visibility culling: culling cuts components apart
+        from . import components
+        rec, stats = components.keep_components(rec, min_area=args.min_component_area or 0.0, largest=args.largest_components, return_stats=True)
+        filtered = {"min_component_area": args.min_component_area, "largest_components": args.largest_components,
+                    "rec_components": len(stats), "rec_components_kept": int((stats.kept & (stats.faces > 0)).sum())}      # what the filtered mesh has
     if args.frames is not None:
         from . import visibility
         with np.load(args.frames) as fr:
@@ -271,12 +281,12 @@ def main(argv=None):
         rec, gt = (None if m is None else visibility.cull_to_views(m, depth, t_wc, intrinsics, args.occlusion_eps) for m in (rec, gt))
     m = None if rec is None or gt is None else calc_3d_metric(rec, gt, N=args.n, seed=args.seed)
     if m is None:
-        print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None}))
+        print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None, **filtered}))
         return 1
     culled = {} if args.frames is None else {"frames": args.frames, "occlusion_eps": args.occlusion_eps, "rec_faces": len(rec.faces),
                                              "gt_faces": len(gt.faces)}
     print(json.dumps({"rec": args.rec, "gt": args.gt, "n": args.n, "seed": args.seed, "accuracy": m[0][0], "completion": m[1][0],
-                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0], **culled}))
+                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0], **culled, **filtered}))
     return 0
 
 

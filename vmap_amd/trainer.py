@@ -31,12 +31,16 @@ class Trainer:
         self.pe = fields.UniDirsEmbed(max_deg=self.n_unidir_funcs, scale=self.obj_scale).to(self.device)
 
     @torch.no_grad()
-    def meshing(self, bound, obj_center, grid_dim=256):
+    def meshing(self, bound, obj_center, grid_dim=256, min_component_area=None, largest_components=None):
         """The reference's Trainer.meshing (trainer.py:35-75) on the device: grid_dim^3 grid points of the object box (scale
         bound.extent / (2 bound_extent), rotation bound.R, centre bound.center, minus obj_center) -> eval_points -> marching cubes at
         0.5 with the vertices mapped to scene coordinates (obj_center NOT subtracted, as in the reference) -> eval_points at the
         vertices -> colours (color * 255) truncated to uint8.  ``bound``: anything with .extent, .center, .R (meshing.BoundingBox,
-        an open3d OrientedBoundingBox).  Returns a meshing.Mesh, or None where the reference returns None."""
+        an open3d OrientedBoundingBox).  Returns a meshing.Mesh, or None where the reference returns None.
+
+        ``min_component_area`` (m^2) and / or ``largest_components`` (k) drop floaters (``components.keep_components``) after
+        marching cubes and BEFORE the colour query, so a dropped vertex is never queried; ``None`` when nothing is left.  Both
+        off (the default): the reference's behaviour."""
         from . import meshing
         D = int(grid_dim)
         dev = torch.device(self.device)
@@ -49,6 +53,13 @@ class Trainer:
         mesh = meshing.extract_mesh(occ.view(D, D, D), 0.5, meshing.bound_affine(bound, self.bound_extent, D))
         if mesh is None:
             return None
+        if min_component_area is not None or largest_components is not None:
+            from . import components
+            with torch.cuda.device(dev):
+                mesh = components.keep_components(mesh, min_area=0.0 if min_component_area is None else min_component_area,
+                                                  largest=largest_components)
+            if mesh is None:
+                return None
         ret = self.eval_points(mesh.vertices)
         if ret is None:
             return None
