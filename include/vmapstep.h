@@ -744,6 +744,82 @@ int vmapstep_components_label(const int32_t* faces, int64_t n_faces, int64_t n_v
 int vmapstep_components_stats(const float* vertices, const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_vertices,
                               int64_t n_components, int32_t* comp_vertices, int64_t* comp_faces, int64_t* comp_area_q, void* stream);
 
+/* ---- mesh rasteriser: depth and face images of a mesh from poses, and the comparison of two depth stacks ------------------------------
+ * What a camera at each of a set of poses sees of an indexed triangle mesh: per pixel the depth along the optical axis and the face
+ * that is nearest there.  The reference gets such images from an outside simulator; the contract below is this project's own
+ * (csrc/raster_rules.h is the definition).
+ *
+ * Camera: the cull section's.  t_wc (DEVICE float32 [slots][4][4], camera to world, row-major; T = its first 12 floats, the rotation
+ * ASSUMED orthonormal); view k of a call reads slot slots[k] (DEVICE int32 [n_views]) or slot k when slots is NULL.  In float32 with
+ * every fma ONE fused operation, every other operation rounded on its own and IEEE division:
+ *   q = p - t;  c_i = fma(T[8 + i], q2, fma(T[4 + i], q1, T[i] * q0));  z = c_2;  u = fma(fx, c_0 / z, cx), v = fma(fy, c_1 / z, cy).
+ * Pixel (w, h) has its centre at u = w, v = h.  Images are [width][height], width-major.
+ *
+ * Which faces take part.  A face (faces: DEVICE int32 [n_faces][3] over vertices: DEVICE float32 [n_vertices][3]) takes part in a view
+ * iff all three indices lie in [0, n_vertices) and all three corners have z > min_depth (min_depth > 0) and |u| <= 16384 and
+ * |v| <= 16384, compared as floats so that a NaN fails.  Any other face is dropped for that view and counted in dropped[view].  There
+ * is NO near-plane clipping: a face with one corner at or behind min_depth is dropped whole - harmless for meshes whose triangles are
+ * small against their distance, and dropped[] is the visible sign of it.  An all-zero pose gives z = 0: every face is dropped.
+ *
+ * Snapping: X = (int)rintf(u * 256), Y likewise (half to even; the product is exact).  |X|, |Y| <= 2^22, and width, height <= 16384, so
+ * every difference is at most 2^23 and every product below at most 2^46: coverage is exact in int64.
+ *
+ * Coverage.  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0); A == 0 covers nothing; with A < 0 corners 1 and 2 change places (their depths
+ * with them: both windings are the same face).  For the centre P = (256 w, 256 h) and the edge a -> b opposite each corner
+ * (1 -> 2, 2 -> 0, 0 -> 1): E = (bx - ax)(Py - ay) - (by - ay)(Px - ax).  The pixel is covered iff for every edge E > 0, or E == 0 and
+ * the edge's direction is lexicographically positive (dy > 0, or dy == 0 and dx > 0): two faces that share an edge with the same
+ * snapped ends cover a centre on it exactly once.  No back-face culling.
+ *
+ * Depth, perspective-correct, a function of (face, pixel) alone, in float64 with NO fused operation, every operation rounded on its own:
+ *   i_k = 1.0 / (double)z_k;  l_k = (double)E_k / (double)A;  r = (l_0 i_0 + l_1 i_1) + l_2 i_2;  z = (float)(1.0 / r).
+ * A pixel whose z is not finite, not > min_depth or - with max_depth > 0 - > max_depth is not written.
+ *
+ * Winner: the smallest 64-bit key (bits(z) << 32) | face; equal depths go to the smaller face index.  keys: DEVICE uint64
+ * [n_views][width][height], all ones where nothing was drawn.  One pass of 64-bit atomic minima: the images depend on the input alone,
+ * not on schedule, launch shape, chunking or run.
+ *
+ * Calls, all enqueued on `stream`, nothing waits:
+ *   vmapstep_raster_count    sets keys to all ones and dropped (DEVICE int32 [n_views]) to 0, draws every face whose box holds at most
+ *                            4 x 4 pixel centres, and counts the others: counts (DEVICE int64 [2]) = {large faces, (view, face, 8 x 8
+ *                            tile) pairs}.  The caller reads them - the one host synchronisation - and, where large faces > 0, calls
+ *   vmapstep_raster_draw     with the same cfg, mesh, poses, keys and workspace, the two counts, and `large`: DEVICE memory, 256-byte
+ *                            aligned, *large_bytes of vmapstep_raster_workspace_bytes(..., large_cap, ...) with large_cap >= n_large.
+ *                            Writes one record per large face - never at or past large_cap, whatever the device's own counts say -
+ *                            and draws the pairs, one wave each.  No lane's work grows with a face's screen area.
+ *   vmapstep_raster_resolve  per pixel of keys (n_pixels = views x width x height): depth (DEVICE float32; 0 where empty), face (DEVICE
+ *                            int32; -1 where empty) and, where given, label = face_labels[face] (DEVICE int32 [n_faces]; -1 where
+ *                            empty) and face_seen[face] = 1 (DEVICE uint8 [n_faces]: byte stores of 1 only, so views may be marked
+ *                            in chunks across calls).  label needs face_labels.
+ *   vmapstep_depth_compare   a, b: DEVICE float32 [n_views][pixels_per_view]; out: DEVICE int64 [n_views][4] = {n_both, n_a_only,
+ *                            n_b_only, sum_q}, zeroed by the call.  A value > 0 is a measurement (a NaN is none).  For a pixel both
+ *                            measured: |a - b| is one rounded float32 subtraction, then rint((double)x * 2^20), half to even: units of
+ *                            2^-20 m; a difference that is not finite counts 0, one pixel is clamped at 2^40 units.  Integer sums:
+ *                            exact, identical from run to run.  Depth L1 of a view in metres = sum_q / 2^20 / n_both.
+ * Workspace: 256-byte aligned, >= *workspace_bytes of vmapstep_raster_workspace_bytes(n_faces, n_views, ...) (VMAPSTEP_ERR_WORKSPACE
+ * otherwise, and for `large`).
+ *
+ * VMAPSTEP_ERR_ARGUMENT before anything is enqueued: a null pointer that would be read or written; width or height outside
+ * 1 .. 16384; min_depth not finite or <= 0; max_depth NaN; fx, fy, cx, cy not finite or fx, fy zero; n_views outside 1 .. 65535;
+ * a count that is negative or >= 2^31; faces without vertices; n_large > large_cap; n_large == 0 with n_pairs > 0; label without
+ * face_labels.  n_faces == 0 is VMAPSTEP_OK: empty images. */
+typedef struct vmapstep_raster_cfg {
+    float fx, fy, cx, cy;
+    float min_depth;               /* > 0 */
+    float max_depth;               /* > 0: the far bound; <= 0: none */
+    int32_t width, height;
+} vmapstep_raster_cfg;
+
+int vmapstep_raster_workspace_bytes(int64_t n_faces, int32_t n_views, int64_t large_cap, size_t* workspace_bytes, size_t* large_bytes);
+int vmapstep_raster_count(const vmapstep_raster_cfg* cfg, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                          const float* t_wc, const int32_t* slots, int32_t n_views, uint64_t* keys, int32_t* dropped, int64_t* counts,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_raster_draw(const vmapstep_raster_cfg* cfg, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                         const float* t_wc, const int32_t* slots, int32_t n_views, uint64_t* keys, int64_t n_large, int64_t n_pairs,
+                         void* large, int64_t large_cap, size_t large_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_raster_resolve(const uint64_t* keys, int64_t n_pixels, float* depth, int32_t* face, const int32_t* face_labels, int64_t n_faces,
+                            int32_t* label, uint8_t* face_seen, void* stream);
+int vmapstep_depth_compare(const float* a, const float* b, int32_t n_views, int64_t pixels_per_view, int64_t* out, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

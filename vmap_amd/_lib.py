@@ -150,6 +150,12 @@ class CullCfg(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("margin", ctypes.c_int32), ("use_depth", ctypes.c_int32)]
 
 
+class RasterCfg(ctypes.Structure):
+    """vmapstep_raster_cfg: the camera, the depth bounds and the image size of the vmapstep_raster_* calls."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -167,6 +173,7 @@ EXPORTS = (
     "vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write", "vmapstep_voxel_points",
     "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count", "vmapstep_cull_faces_emit",
     "vmapstep_components_workspace_bytes", "vmapstep_components_label", "vmapstep_components_stats",
+    "vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve", "vmapstep_depth_compare",
 )
 
 _libs = {}
@@ -312,6 +319,19 @@ def load(path=None):
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.vmapstep_components_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    _mesh_views = [ctypes.POINTER(RasterCfg), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.c_int32, ctypes.c_void_p]
+    lib.vmapstep_raster_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t),
+                                                    ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_raster_count.argtypes = _mesh_views + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_raster_draw.argtypes = _mesh_views + [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t,
+                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_raster_resolve.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_depth_compare.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    for fn in ("vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve",
+               "vmapstep_depth_compare"):
+        getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
                "vmapstep_voxel_points", "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count",
                "vmapstep_cull_faces_emit", "vmapstep_components_workspace_bytes", "vmapstep_components_label", "vmapstep_components_stats"):

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip, k_components.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip, k_components.hip, k_raster.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@ namespace vk { struct WsArgs; }
 struct vmapstep_ingest_cfg;
 struct vmapstep_filter_cfg;
 struct vmapstep_cull_cfg;
+struct vmapstep_raster_cfg;
 
 namespace vl {
 
@@ -143,5 +144,17 @@ int cull_faces_emit(const int* faces, long long n_faces, const unsigned char* se
 int components_label(const int* faces, long long n_faces, long long n_vertices, int* labels, long long* counts, void* workspace, hipStream_t st);
 int components_stats(const float* vertices, const int* faces, long long n_faces, const int* labels, long long n_vertices, long long n_components,
                      int* comp_vertices, long long* comp_faces, long long* comp_area_q, hipStream_t st);
+
+// k_raster.hip: the mesh rasteriser (raster_kernels.h).  raster_count = keys to all ones, dropped to 0, raster_setup (small faces are
+// drawn there), raster_scan -> counts {large faces, pairs} on the workspace of vl::raster_layout; raster_draw = the large-face buffer
+// to 0, raster_emit, raster_tiles on the workspace the count call left; raster_resolve; depth_compare zeroes `out`, then adds.
+int raster_count(const vmapstep_raster_cfg& cfg, const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float* t_wc,
+                 const int* slots, int n_views, unsigned long long* keys, int* dropped, long long* counts, void* workspace, hipStream_t st);
+int raster_draw(const vmapstep_raster_cfg& cfg, const float* vertices, long long n_vertices, const int* faces, long long n_faces, const float* t_wc,
+                const int* slots, int n_views, unsigned long long* keys, long long n_large, long long n_pairs, void* large, long long large_cap,
+                void* workspace, hipStream_t st);
+int raster_resolve(const unsigned long long* keys, long long n_pixels, float* depth, int* face, const int* face_labels, long long n_faces, int* label,
+                   unsigned char* face_seen, hipStream_t st);
+int depth_compare(const float* a, const float* b, int n_views, long long pixels, long long* out, hipStream_t st);
 
 }  // namespace vl

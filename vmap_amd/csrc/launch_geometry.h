@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, cull and component families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h, component_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, cull, component and raster families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h, component_kernels.h, raster_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -89,6 +89,20 @@ constexpr int kCompScanWG = 256;           // the single workgroup of comp_scan
 constexpr int kStatsWG = 1024;             // comp_face_stats / comp_vertex_stats: sixteen waves share one LDS table before the global atomics
 constexpr int kStatsSlots = 64;            // rows of that table, keyed by component % kStatsSlots (a second component on a row goes straight to memory)
 }  // namespace vcc
+
+namespace vr {
+constexpr int kRasterWG = 256;             // raster_setup / _emit: (view, face) pairs per block, one view per block row; raster_tiles: four waves
+constexpr int kRasterScanWG = 1024;        // the single workgroup of raster_scan
+constexpr int kScanPer = 8;                // consecutive block totals per lane of raster_scan: 8192 blocks per round
+constexpr int kTilesPerWG = kRasterWG / 64;        // (view, face, tile) pairs per raster_tiles workgroup per round: one wave each
+constexpr long long kMaxTileBlocks = 1ll << 20;    // grid of raster_tiles: beyond 4 M pairs a wave takes every (grid x 4)-th pair
+constexpr int kLargeRecInts = 16;          // one large-face record: 64 bytes
+constexpr int kResolveWG = 256;            // raster_resolve: one pixel per lane
+constexpr int kCompareWG = 256;            // depth_compare
+constexpr int kComparePer = 4;             // pixels per lane of depth_compare, kCompareWG apart
+constexpr int kCompareBlock = kCompareWG * kComparePer;
+constexpr int kCompareInts = 4;            // a view's row: n_both, n_a_only, n_b_only, sum_q
+}  // namespace vr
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -324,6 +338,22 @@ inline ComponentLayout component_layout(long long n_vertices, long long n_faces)
     l.off_dense = ws_up((size_t)n_vertices * sizeof(int));
     l.off_vblk = l.off_dense + ws_up((size_t)n_vertices * sizeof(int));
     l.bytes = l.off_vblk + ws_up((size_t)l.nvb * sizeof(long long)) + 256;
+    return l;
+}
+
+// The mesh rasteriser.  The workspace of the count call: per (view, block of vr::kRasterWG faces) an int64 pair - the block's large faces
+// and their (view, face, tile) pairs, then (after raster_scan) their exclusive prefixes.  The large-face buffer the draw call fills:
+// the first pair of every large face (int64 [large_cap]) and its record (vr::kLargeRecInts int32 each).
+struct RasterLayout {
+    int nfb; long long nblk; size_t bytes, off_rec, large_bytes;
+};
+inline RasterLayout raster_layout(long long n_faces, int n_views, long long large_cap) {
+    RasterLayout l;
+    l.nfb = (int)ceil_div(n_faces, vr::kRasterWG);
+    l.nblk = (long long)l.nfb * n_views;
+    l.bytes = ws_up((size_t)l.nblk * 2 * sizeof(long long)) + 256;
+    l.off_rec = ws_up((size_t)large_cap * sizeof(long long)) + 256;
+    l.large_bytes = l.off_rec + ws_up((size_t)large_cap * vr::kLargeRecInts * sizeof(int)) + 256;
     return l;
 }
 

@@ -1229,6 +1229,89 @@ int vmapstep_components_stats(const float* vertices, const int32_t* faces, int64
                                 reinterpret_cast<long long*>(comp_area_q), static_cast<hipStream_t>(stream));
 }
 
+// ---- mesh rasteriser ----------------------------------------------------------------------------------------------------------------
+static int check_raster_cfg(const vmapstep_raster_cfg* cfg) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: cfg is null");
+    if (cfg->width < 1 || cfg->height < 1 || cfg->width > 16384 || cfg->height > 16384)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster: width=%d height=%d outside 1 .. 16384", cfg->width, cfg->height);
+    if (!(cfg->min_depth > 0.0f) || !std::isfinite(cfg->min_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: min_depth must be finite and > 0");
+    if (std::isnan(cfg->max_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: max_depth is not a number");
+    if (!std::isfinite(cfg->fx) || !std::isfinite(cfg->fy) || !std::isfinite(cfg->cx) || !std::isfinite(cfg->cy) || cfg->fx == 0.0f || cfg->fy == 0.0f)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster: intrinsics must be finite with fx, fy != 0");
+    return VMAPSTEP_OK;
+}
+
+static int check_raster_sizes(int64_t n_vertices, int64_t n_faces, int32_t n_views) {
+    if (n_vertices < 0 || n_vertices >= (1ll << 31) || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster: n_vertices=%lld n_faces=%lld outside 0 .. 2^31 - 1", (long long)n_vertices, (long long)n_faces);
+    if (n_views < 1 || n_views > 65535) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: n_views=%d outside 1 .. 65535", n_views);
+    if (n_faces > 0 && n_vertices == 0) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: %lld faces and no vertex", (long long)n_faces);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_raster_workspace_bytes(int64_t n_faces, int32_t n_views, int64_t large_cap, size_t* workspace_bytes, size_t* large_bytes) {
+    if (!workspace_bytes || !large_bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "raster: null argument");
+    if (int rc = check_raster_sizes(0, 0, n_views)) return rc;
+    if (n_faces < 0 || n_faces >= (1ll << 31) || large_cap < 0 || large_cap >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster: n_faces=%lld large_cap=%lld outside 0 .. 2^31 - 1", (long long)n_faces, (long long)large_cap);
+    const vl::RasterLayout l = vl::raster_layout(n_faces, n_views, large_cap);
+    *workspace_bytes = l.bytes;
+    *large_bytes = l.large_bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_raster_count(const vmapstep_raster_cfg* cfg, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                          const float* t_wc, const int32_t* slots, int32_t n_views, uint64_t* keys, int32_t* dropped, int64_t* counts,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_raster_cfg(cfg)) return rc;
+    if (int rc = check_raster_sizes(n_vertices, n_faces, n_views)) return rc;
+    if (!t_wc || !keys || !dropped || !counts || (n_faces > 0 && (!faces || !vertices))) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_count: null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::raster_layout(n_faces, n_views, 0).bytes, "raster")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::raster_count(*cfg, vertices, n_vertices, reinterpret_cast<const int*>(faces), n_faces, t_wc, reinterpret_cast<const int*>(slots), n_views,
+                            reinterpret_cast<unsigned long long*>(keys), reinterpret_cast<int*>(dropped), reinterpret_cast<long long*>(counts),
+                            workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_raster_draw(const vmapstep_raster_cfg* cfg, const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                         const float* t_wc, const int32_t* slots, int32_t n_views, uint64_t* keys, int64_t n_large, int64_t n_pairs,
+                         void* large, int64_t large_cap, size_t large_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_raster_cfg(cfg)) return rc;
+    if (int rc = check_raster_sizes(n_vertices, n_faces, n_views)) return rc;
+    if (n_large < 0 || n_pairs < 0 || large_cap < 0 || large_cap >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster_draw: n_large=%lld n_pairs=%lld large_cap=%lld", (long long)n_large, (long long)n_pairs, (long long)large_cap);
+    if (n_large > large_cap) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_draw: large_cap=%lld is too small for %lld large faces", (long long)large_cap, (long long)n_large);
+    if (n_large == 0 && n_pairs > 0) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_draw: %lld pairs of no large face", (long long)n_pairs);
+    if (n_large > n_faces * (int64_t)n_views) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_draw: n_large=%lld exceeds views x faces", (long long)n_large);
+    if (!t_wc || !keys || (n_faces > 0 && (!faces || !vertices))) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_draw: null argument");
+    if (int rc = check_eval_workspace(workspace, workspace_bytes, vl::raster_layout(n_faces, n_views, 0).bytes, "raster")) return rc;
+    if (n_large == 0 || n_pairs == 0) return VMAPSTEP_OK;  // nothing to draw: nothing enqueued
+    if (int rc = check_eval_workspace(large, large_bytes, vl::raster_layout(n_faces, n_views, large_cap).large_bytes, "raster large-face")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::raster_draw(*cfg, vertices, n_vertices, reinterpret_cast<const int*>(faces), n_faces, t_wc, reinterpret_cast<const int*>(slots), n_views,
+                           reinterpret_cast<unsigned long long*>(keys), n_large, n_pairs, large, large_cap, workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_raster_resolve(const uint64_t* keys, int64_t n_pixels, float* depth, int32_t* face, const int32_t* face_labels, int64_t n_faces,
+                            int32_t* label, uint8_t* face_seen, void* stream) {
+    if (n_pixels < 0 || n_faces < 0 || n_faces >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raster_resolve: n_pixels=%lld n_faces=%lld", (long long)n_pixels, (long long)n_faces);
+    if (label && !face_labels) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_resolve: label without face_labels");
+    if (n_pixels == 0) return VMAPSTEP_OK;
+    if (!keys || !depth || !face) return fail(VMAPSTEP_ERR_ARGUMENT, "raster_resolve: null argument");
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::raster_resolve(reinterpret_cast<const unsigned long long*>(keys), n_pixels, depth, reinterpret_cast<int*>(face),
+                              reinterpret_cast<const int*>(face_labels), n_faces, reinterpret_cast<int*>(label), face_seen, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_depth_compare(const float* a, const float* b, int32_t n_views, int64_t pixels_per_view, int64_t* out, void* stream) {
+    if (n_views < 1 || n_views > 65535 || pixels_per_view < 1 || pixels_per_view >= (1ll << 31))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "depth_compare: n_views=%d (1 .. 65535) pixels_per_view=%lld (1 .. 2^31 - 1)", n_views, (long long)pixels_per_view);
+    if (!a || !b || !out) return fail(VMAPSTEP_ERR_ARGUMENT, "depth_compare: null argument");
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::depth_compare(a, b, n_views, pixels_per_view, reinterpret_cast<long long*>(out), static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

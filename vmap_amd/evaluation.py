@@ -263,30 +263,56 @@ def main(argv=None):
     ap.add_argument("--min-component-area", type=float, default=None, metavar="X",
                     help="drop the components of REC (floaters) whose area is below X square metres, before any culling")
     ap.add_argument("--largest-components", type=int, default=None, metavar="K", help="keep only the K largest components of REC by area")
+    ap.add_argument("--render-gt-depth", action="store_true",
+                    help="with --frames: rasterise GT from the poses (the file needs t_wc, intrinsics and size = [width, height], no depth); "
+                         "GT is culled to the faces that won a pixel, REC against GT's rasterised depth")
+    ap.add_argument("--depth-l1", action="store_true",
+                    help="with --frames: add depth_l1 (metres), depth_both_share and depth_gt_only_share of REC against GT, both rasterised "
+                         "from the poses as loaded, before any culling")
+    ap.add_argument("--min-raster-depth", type=float, default=0.05, metavar="X",
+                    help="the rasteriser's near bound in metres: a face with a corner nearer than X is not drawn (default 0.05)")
     args = ap.parse_args(argv)
     rec, gt = load_mesh(args.rec), load_mesh(args.gt)
     if args.frames is None and args.occlusion_eps is not None:
         ap.error("--occlusion-eps needs --frames")
-    filtered = {}
+    if args.frames is None and (args.render_gt_depth or args.depth_l1):
+        ap.error("--render-gt-depth and --depth-l1 need --frames")
+    filtered, rastered = {}, {}
+    if args.render_gt_depth or args.depth_l1:
+        from . import raster
+        with np.load(args.frames) as fr:
+            r_twc, r_intr = fr["t_wc"], fr["intrinsics"]
+            r_w, r_h = (int(x) for x in (fr["size"] if "size" in fr.files else fr["depth"].shape[1:]))
+        view = dict(min_depth=args.min_raster_depth)
+        if args.depth_l1:
+            d = raster.depth_l1(rec, gt, r_twc, r_intr, r_w, r_h, **view)
+            pixels = float(len(d["n_both"]) * r_w * r_h)
+            rastered = {"depth_l1": d["depth_l1"], "depth_both_share": int(d["n_both"].sum()) / pixels,
+                        "depth_gt_only_share": int(d["n_b_only"].sum()) / pixels}
     if args.min_component_area is not None or args.largest_components is not None:
         # REC only, and before visibility culling: culling cuts components apart
         from . import components
         rec, stats = components.keep_components(rec, min_area=args.min_component_area or 0.0, largest=args.largest_components, return_stats=True)
         filtered = {"min_component_area": args.min_component_area, "largest_components": args.largest_components,
                     "rec_components": len(stats), "rec_components_kept": int((stats.kept & (stats.faces > 0)).sum())}      # what the filtered mesh has
-    if args.frames is not None:
+    if args.render_gt_depth:
+        from . import visibility
+        gt_depth = raster.rasterize(gt, r_twc, r_intr, r_w, r_h, **view).depth
+        rec = None if rec is None else visibility.cull_to_views(rec, gt_depth, r_twc, r_intr, args.occlusion_eps)
+        gt = raster.cull_to_raster(gt, r_twc, r_intr, r_w, r_h, **view)
+    elif args.frames is not None:
         from . import visibility
         with np.load(args.frames) as fr:
             depth, t_wc, intrinsics = fr["depth"], fr["t_wc"], fr["intrinsics"]
         rec, gt = (None if m is None else visibility.cull_to_views(m, depth, t_wc, intrinsics, args.occlusion_eps) for m in (rec, gt))
     m = None if rec is None or gt is None else calc_3d_metric(rec, gt, N=args.n, seed=args.seed)
     if m is None:
-        print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None, **filtered}))
+        print(json.dumps({"rec": args.rec, "gt": args.gt, "result": None, **filtered, **rastered}))
         return 1
     culled = {} if args.frames is None else {"frames": args.frames, "occlusion_eps": args.occlusion_eps, "rec_faces": len(rec.faces),
                                              "gt_faces": len(gt.faces)}
     print(json.dumps({"rec": args.rec, "gt": args.gt, "n": args.n, "seed": args.seed, "accuracy": m[0][0], "completion": m[1][0],
-                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0], **culled, **filtered}))
+                      "completion_ratio_1cm": m[2][0], "completion_ratio_5cm": m[3][0], **culled, **filtered, **rastered}))
     return 0
 
 

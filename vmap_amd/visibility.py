@@ -9,7 +9,8 @@ own - the reference leaves the step to outside tools.
 
 The known limit: a face is judged by its corners.  A large triangle whose corners all miss every frustum is dropped even if its
 middle was seen (coarse ground-truth meshes have such triangles).  The remedy is to cull samples, not vertices: draw the points with
-``evaluation.sample_surface`` and pass them to ``mark_visible``."""
+``evaluation.sample_surface`` and pass them to ``mark_visible`` - or to cull by what won a pixel: ``raster.cull_to_raster`` keeps
+exactly the faces that are nearest somewhere in some view."""
 from __future__ import annotations
 
 import ctypes
