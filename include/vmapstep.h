@@ -652,6 +652,88 @@ int vmapstep_filter_write(const vmapstep_filter_cfg* cfg, const void* depth, con
 int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* offsets, int32_t n_seg, float voxel_size,
                           float* points, float* bounds, void* stream);
 
+/* ---- track: per-frame detections to persistent instance ids -----------------------------------------------------------------------
+ * What the reference's track_instance does on the host per frame (utils.py:274-382), several full-frame passes per detector mask
+ * there.  A detector numbers its masks afresh in every frame; this decides which known instance each mask is.  Inputs as the filter's,
+ * DEVICE pointers, row-major [height][width]: depth uint16 or float32 (cfg.depth_f32), det - the detector's label image - uint16 or
+ * int32 (cfg.label_i32).  Pixel, depth, validity, world point, eroded mask, box-table row, inside test and voxel key are the filter
+ * section's, word for word (csrc/filter_rules.h; csrc/track_rules.h adds the decision).  Nothing here could be held against Open3D or
+ * OpenCV: neither was available where this was written.
+ *
+ * Rows.  d = raw + det_shift is a pixel's detection row; rows lie in [0, max_det), pixels with any other row are counted in
+ * `overflow`; row 0 means "no detection".  Rows [0, n_det) have a class.  Persistent ids lie in [1, max_ids); box_table (DEVICE
+ * float32 [max_ids][16]) is indexed by persistent id.
+ *
+ * meta (DEVICE int32 [max_det + max_det + 1 + max_pairs]) is laid out by the caller before the launch:
+ *   det_class[max_det]     the class of row d (rows >= n_det: ignored)
+ *   pair_off[max_det + 1]  an exclusive prefix over rows: the candidates of row d are the pairs [pair_off[d], pair_off[d + 1])
+ *   pair_inst[max_pairs]   pair p's persistent id: the registered instances of the row's class in ascending id
+ * n_pairs = pair_off[max_det].  An offset outside [0, n_pairs] is clipped and a pair_inst outside [0, max_ids) counts nothing.
+ *
+ * Per row, in one pass: pixels, valid, eroded, eroded_valid (the filter's definitions) and, for every pair p of the row, inside[p] =
+ * the row's valid pixels whose world point is inside box_table[pair_inst[p]] as it is when the call runs.  Status, first match:
+ *   VMAPSTEP_TRACK_ABSENT       pixels == 0
+ *   VMAPSTEP_TRACK_BACKGROUND   d == 0, or the class is one of background_classes[0 .. n_background)
+ *   VMAPSTEP_TRACK_SMALL        eroded <= min_pixels          (<=, as utils.py:290; box_filter uses <)
+ *   VMAPSTEP_TRACK_FEW_POINTS   eroded_valid <= min_points
+ *   VMAPSTEP_TRACK_MERGED       into the FIRST pair of the row, in order, with (int64(inside) << 16) > int64(ratio_q) * valid, where
+ *                               ratio_q = round(match_ratio * 65536); a later pair with a higher ratio does not win
+ *   VMAPSTEP_TRACK_NEW          otherwise; its id is next_id + its rank among the frame's NEW rows in ascending d
+ * (VMAPSTEP_TRACK_NEW_NO_BOX is never written by the library: the caller patches it into `status` when the cloud of a NEW row turns
+ * out to have no box.)  The values are the filter's status values.  The library does not check next_id + rank against max_ids: the
+ * caller does, from the rows, before it uses an id.
+ *
+ * vmapstep_track_stats (track_init, track_stats, track_decide) fills status and ident (DEVICE int32 [max_det] each; ident = the
+ * persistent id of a NEW or MERGED row, else 0) and rows_out (DEVICE int32 [4 + max_det * 9 + max_pairs]): n_rows, overflow, 0, 0,
+ * then n_rows rows of (d, status, class, id, pixels, valid, inside of the matched pair or 0, eroded, eroded_valid) in ascending d;
+ * inside[p] of every pair starts at rows_out[4 + max_det * 9].  vmapstep_track_emit (track_count, track_scan, track_emit), on the
+ * same workspace after it, writes in pixel order into keys_out (DEVICE uint64 [width * height]) the voxel keys, under ident[d], of
+ * the valid eroded pixels of NEW rows and of the valid pixels of MERGED rows that are inside box_table[ident[d]]; rows_out[2] = the
+ * number of keys, rows_out[3] = out_of_grid.  vmapstep_track_write writes labels_out (DEVICE int32 [H][W]) from status and ident as
+ * the caller left them: ident for NEW; for MERGED -1 where the pixel is valid and outside box_table[ident], else ident; 0 otherwise.
+ * box_table must be the same in all three calls: the table the frame arrived to.
+ * All combining is an integer sum and keys are written in pixel order: the output is bit-identical from call to call.
+ *
+ * Everything is enqueued on `stream`, nothing waits.  Refused before anything is enqueued: null or inconsistent arguments (n_det
+ * outside [0, max_det], n_pairs < 0, next_id outside [1, max_ids], ratio_q < 0: VMAPSTEP_ERR_ARGUMENT); width or height above 4095,
+ * max_det outside [1, 4096], max_pairs outside [1, 65536], n_pairs > max_pairs, max_ids outside [2, 32767], erode_radius outside
+ * [0, 8], more than 64 classes (VMAPSTEP_ERR_UNSUPPORTED); a workspace that is not 256-byte aligned or smaller than
+ * vmapstep_track_workspace_bytes(cfg) (VMAPSTEP_ERR_WORKSPACE). */
+#define VMAPSTEP_TRACK_ROW_INTS 9
+#define VMAPSTEP_TRACK_HEAD_INTS 4
+#define VMAPSTEP_TRACK_MAX_DET 4096
+#define VMAPSTEP_TRACK_MAX_PAIRS 65536
+#define VMAPSTEP_TRACK_PAIR_SLOTS 64   /* (detection, candidate) pairs one track_stats workgroup holds in LDS; more go to global memory */
+#define VMAPSTEP_TRACK_ABSENT VMAPSTEP_FILTER_ABSENT
+#define VMAPSTEP_TRACK_NEW VMAPSTEP_FILTER_NEW
+#define VMAPSTEP_TRACK_MERGED VMAPSTEP_FILTER_MERGED
+#define VMAPSTEP_TRACK_BACKGROUND VMAPSTEP_FILTER_BACKGROUND
+#define VMAPSTEP_TRACK_FEW_POINTS VMAPSTEP_FILTER_FEW_POINTS
+#define VMAPSTEP_TRACK_SMALL VMAPSTEP_FILTER_SMALL
+#define VMAPSTEP_TRACK_NEW_NO_BOX VMAPSTEP_FILTER_NEW_NO_BOX
+typedef struct vmapstep_track_cfg {
+    int32_t width, height;
+    int32_t depth_f32;             /* depth: 0 = uint16, 1 = float32 */
+    int32_t label_i32;             /* det: 0 = uint16, 1 = int32 */
+    float depth_scale, max_depth;
+    float fx, fy, cx, cy;
+    float t_wc[16];
+    float voxel_size;
+    int32_t det_shift, min_pixels, min_points, erode_radius;
+    int32_t max_det, max_pairs, max_ids;
+    int32_t n_det, n_pairs, next_id, ratio_q;
+    int32_t n_background;
+    int32_t background_classes[VMAPSTEP_FILTER_MAX_CLASSES];
+} vmapstep_track_cfg;
+
+int vmapstep_track_workspace_bytes(const vmapstep_track_cfg* cfg, size_t* bytes);
+int vmapstep_track_stats(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const int32_t* meta, const float* box_table,
+                         int32_t* status, int32_t* ident, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_track_emit(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const float* box_table, const int32_t* status,
+                        const int32_t* ident, uint64_t* keys_out, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_track_write(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const float* box_table, const int32_t* status,
+                         const int32_t* ident, int32_t* labels_out, void* stream);
+
 /* ---- visibility culling: what the keyframes saw of a cloud, and a mesh compacted by such a mask ---------------------------------------
  * Scene-level evaluation first removes, from the reconstruction and from the ground truth, what no frame observed.  The reference
  * leaves that to outside tools; the contract below is this project's own (csrc/cull_rules.h is the definition).

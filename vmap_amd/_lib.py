@@ -143,6 +143,25 @@ FILTER_MAX_IDS = 32767
 FILTER_MAX_RADIUS = 8
 
 
+class TrackCfg(ctypes.Structure):
+    """vmapstep_track_cfg: the frame shape, the input types, the camera, the rules and the frame's counts of the vmapstep_track_* calls."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("depth_f32", ctypes.c_int32), ("label_i32", ctypes.c_int32),
+                ("depth_scale", ctypes.c_float), ("max_depth", ctypes.c_float),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("t_wc", ctypes.c_float * 16), ("voxel_size", ctypes.c_float),
+                ("det_shift", ctypes.c_int32), ("min_pixels", ctypes.c_int32), ("min_points", ctypes.c_int32), ("erode_radius", ctypes.c_int32),
+                ("max_det", ctypes.c_int32), ("max_pairs", ctypes.c_int32), ("max_ids", ctypes.c_int32),
+                ("n_det", ctypes.c_int32), ("n_pairs", ctypes.c_int32), ("next_id", ctypes.c_int32), ("ratio_q", ctypes.c_int32),
+                ("n_background", ctypes.c_int32), ("background_classes", ctypes.c_int32 * 64)]
+
+
+TRACK_ROW_INTS = 9                         # d, status, class, persistent id, pixels, valid, inside, eroded, eroded_valid
+TRACK_HEAD_INTS = 4                        # n_rows, overflow, n_keys, out_of_grid
+TRACK_MAX_DET = 4096
+TRACK_MAX_PAIRS = 65536
+TRACK_PAIR_SLOTS = 64                      # pairs one track_stats workgroup holds in LDS; more go to global memory directly
+
+
 class CullCfg(ctypes.Structure):
     """vmapstep_cull_cfg: the camera, the image size and the mode of one vmapstep_cull_mark call."""
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
@@ -171,6 +190,7 @@ EXPORTS = (
     "vmapstep_scene_view_workspace_bytes", "vmapstep_scene_view_count", "vmapstep_scene_view_render",
     "vmapstep_ingest_workspace_bytes", "vmapstep_ingest_frame",
     "vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write", "vmapstep_voxel_points",
+    "vmapstep_track_workspace_bytes", "vmapstep_track_stats", "vmapstep_track_emit", "vmapstep_track_write",
     "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count", "vmapstep_cull_faces_emit",
     "vmapstep_components_workspace_bytes", "vmapstep_components_label", "vmapstep_components_stats",
     "vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve", "vmapstep_depth_compare",
@@ -306,6 +326,15 @@ def load(path=None):
                                           ctypes.c_void_p, ctypes.c_void_p]
     lib.vmapstep_voxel_points.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_track_workspace_bytes.argtypes = [ctypes.POINTER(TrackCfg), ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_track_stats.argtypes = [ctypes.POINTER(TrackCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_track_emit.argtypes = [ctypes.POINTER(TrackCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_track_write.argtypes = [ctypes.POINTER(TrackCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for fn in ("vmapstep_track_workspace_bytes", "vmapstep_track_stats", "vmapstep_track_emit", "vmapstep_track_write"):
+        getattr(lib, fn).restype = ctypes.c_int
     lib.vmapstep_cull_mark.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                        ctypes.POINTER(CullCfg), ctypes.c_void_p, ctypes.c_void_p]
     lib.vmapstep_cull_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_cull.hip, k_components.hip, k_raster.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 namespace vk { struct WsArgs; }
 struct vmapstep_ingest_cfg;
 struct vmapstep_filter_cfg;
+struct vmapstep_track_cfg;
 struct vmapstep_cull_cfg;
 struct vmapstep_raster_cfg;
 
@@ -127,6 +128,18 @@ int filter_write(const vmapstep_filter_cfg& cfg, const void* depth, const void* 
                  hipStream_t st);
 int voxel_points(const unsigned long long* keys, long long n_keys, const long long* offsets, int n_seg, float voxel, float* points, float* bounds,
                  hipStream_t st);
+
+// k_track.hip: the instance tracker (track_kernels.h).  The workspace is vl::track_layout's; meta holds det_class [max_det], pair_off
+// [max_det + 1] and pair_inst [max_pairs] as int32; rows_out holds 4 + max_det * 9 + max_pairs int32, status and ident max_det int32
+// each, box_table max_ids * 16 float32, keys_out width * height uint64.
+// track_init, track_stats, track_decide:
+int track_stats(const vmapstep_track_cfg& cfg, const void* depth, const void* det, const int* meta, const float* box_table, int* status,
+                int* ident, int* rows_out, void* workspace, hipStream_t st);
+// track_count, track_scan, track_emit, on the workspace track_stats left:
+int track_emit(const vmapstep_track_cfg& cfg, const void* depth, const void* det, const float* box_table, const int* status, const int* ident,
+               unsigned long long* keys_out, int* rows_out, void* workspace, hipStream_t st);
+int track_write(const vmapstep_track_cfg& cfg, const void* depth, const void* det, const float* box_table, const int* status, const int* ident,
+                int* labels_out, hipStream_t st);
 
 // k_cull.hip: visibility culling (cull_kernels.h).  cull_mark only ever turns a 0 of `seen` into a 1.  The compaction's workspace is
 // vl::cull_layout's: cull_faces_count = cull_clear, cull_face_count, cull_vertex_count, cull_scan -> counts {kept faces, kept vertices};

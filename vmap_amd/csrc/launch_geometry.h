@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, cull, component and raster families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, cull_kernels.h, component_kernels.h, raster_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, track, cull, component and raster families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, track_kernels.h, cull_kernels.h, component_kernels.h, raster_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -73,6 +73,14 @@ constexpr int kPixBlock = kFilterWG * kPixPer;
 constexpr int kMaxIds = 32767;
 constexpr int kMaxSide = 4095;
 }  // namespace vf
+
+namespace vt {                             // the instance tracker: the tile, block and replica geometry is vf's
+constexpr int kPairSlots = 64;             // (detection, candidate) pairs the LDS table of one track_stats workgroup holds (a power of two)
+constexpr int kPairProbes = 4;
+constexpr int kStatInts = 4;               // a row of the global table: pixels, valid, eroded, eroded_valid
+constexpr int kMaxDet = 4096;
+constexpr int kMaxPairs = 65536;
+}  // namespace vt
 
 namespace vc {
 constexpr int kCullWG = 256;               // every cull kernel but cull_scan; faces / vertices per block of the compaction
@@ -303,6 +311,22 @@ inline FilterLayout filter_layout(int max_ids, int width, int height) {
     FilterLayout l;
     l.off_table = 256;
     l.off_flags = l.off_table + ws_up((size_t)vf::kReplicas * max_ids * vf::kTableInts * sizeof(int));
+    l.off_blk = l.off_flags + ws_up((size_t)width * height);
+    l.bytes = l.off_blk + ws_up((size_t)filter_pix_blocks(width, height) * 2 * sizeof(int));
+    return l;
+}
+
+// Instance tracker.  The workspace: the overflow word, the statistics of every detection row (int32 [vf::kReplicas][max_det]
+// [vt::kStatInts]), the inside count of every pair (int32 [vf::kReplicas][max_pairs]; track_decide leaves the sum in copy 0), one byte
+// of flags per pixel (valid, eroded) and the (emitted, out of grid) pair of every block of vf::kPixBlock pixels, as the filter's.
+struct TrackLayout {
+    size_t off_table, off_pairs, off_flags, off_blk, bytes;
+};
+inline TrackLayout track_layout(int max_det, int max_pairs, int width, int height) {
+    TrackLayout l;
+    l.off_table = 256;
+    l.off_pairs = l.off_table + ws_up((size_t)vf::kReplicas * max_det * vt::kStatInts * sizeof(int));
+    l.off_flags = l.off_pairs + ws_up((size_t)vf::kReplicas * max_pairs * sizeof(int));
     l.off_blk = l.off_flags + ws_up((size_t)width * height);
     l.bytes = l.off_blk + ws_up((size_t)filter_pix_blocks(width, height) * 2 * sizeof(int));
     return l;

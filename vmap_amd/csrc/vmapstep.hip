@@ -1127,6 +1127,76 @@ int vmapstep_voxel_points(const uint64_t* keys, int64_t n_keys, const int64_t* o
                             voxel_size, points, bounds, static_cast<hipStream_t>(stream));
 }
 
+// ---- instance tracker --------------------------------------------------------------------------------------------------------------
+static int check_track_cfg(const vmapstep_track_cfg* cfg) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "track: cfg is null");
+    if (cfg->width < 1 || cfg->height < 1 || cfg->n_background < 0 || (cfg->depth_f32 | cfg->label_i32) & ~1)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "track: width=%d height=%d n_background=%d depth_f32=%d label_i32=%d", cfg->width, cfg->height,
+                    cfg->n_background, cfg->depth_f32, cfg->label_i32);
+    if (!std::isfinite(cfg->depth_scale) || std::isnan(cfg->max_depth) || !(cfg->voxel_size > 0.0f) || !std::isfinite(cfg->voxel_size))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "track: depth_scale must be finite, max_depth a number, voxel_size finite and > 0");
+    if (cfg->width > vf::kMaxSide || cfg->height > vf::kMaxSide || cfg->n_background > VMAPSTEP_FILTER_MAX_CLASSES)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "track limits: width, height <= %d, n_background <= %d (width=%d height=%d n_background=%d)",
+                    vf::kMaxSide, VMAPSTEP_FILTER_MAX_CLASSES, cfg->width, cfg->height, cfg->n_background);
+    if (cfg->max_det < 1 || cfg->max_det > vt::kMaxDet || cfg->max_pairs < 1 || cfg->max_pairs > vt::kMaxPairs || cfg->max_ids < 2 ||
+        cfg->max_ids > vf::kMaxIds || cfg->erode_radius < 0 || cfg->erode_radius > vf::kMaxRadius)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED,
+                    "track limits: 1 <= max_det <= %d, 1 <= max_pairs <= %d, 2 <= max_ids <= %d, 0 <= erode_radius <= %d (max_det=%d max_pairs=%d "
+                    "max_ids=%d erode_radius=%d)", vt::kMaxDet, vt::kMaxPairs, vf::kMaxIds, vf::kMaxRadius, cfg->max_det, cfg->max_pairs,
+                    cfg->max_ids, cfg->erode_radius);
+    if (cfg->n_pairs > cfg->max_pairs)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "track limits: the frame needs %d pairs, max_pairs = %d", cfg->n_pairs, cfg->max_pairs);
+    if (cfg->n_det < 0 || cfg->n_det > cfg->max_det || cfg->n_pairs < 0 || cfg->next_id < 1 || cfg->next_id > cfg->max_ids || cfg->ratio_q < 0)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "track: n_det=%d (max_det=%d) n_pairs=%d next_id=%d (max_ids=%d) ratio_q=%d", cfg->n_det, cfg->max_det,
+                    cfg->n_pairs, cfg->next_id, cfg->max_ids, cfg->ratio_q);
+    return VMAPSTEP_OK;
+}
+
+static int check_track_workspace(const vmapstep_track_cfg* cfg, const void* workspace, size_t workspace_bytes) {
+    const size_t need = vl::track_layout(cfg->max_det, cfg->max_pairs, cfg->width, cfg->height).bytes;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % kAlign || workspace_bytes < need)
+        return fail(VMAPSTEP_ERR_WORKSPACE, "track workspace must be 256-byte aligned and >= %zu bytes", need);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_track_workspace_bytes(const vmapstep_track_cfg* cfg, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_track_cfg(cfg)) return rc;
+    *bytes = vl::track_layout(cfg->max_det, cfg->max_pairs, cfg->width, cfg->height).bytes;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_track_stats(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const int32_t* meta, const float* box_table,
+                         int32_t* status, int32_t* ident, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg || !depth || !det || !meta || !box_table || !status || !ident || !rows_out) return fail(VMAPSTEP_ERR_ARGUMENT, "track_stats: null argument");
+    if (int rc = check_track_cfg(cfg)) return rc;
+    if (int rc = check_track_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::track_stats(*cfg, depth, det, reinterpret_cast<const int*>(meta), box_table, reinterpret_cast<int*>(status),
+                           reinterpret_cast<int*>(ident), reinterpret_cast<int*>(rows_out), workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_track_emit(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const float* box_table, const int32_t* status,
+                        const int32_t* ident, uint64_t* keys_out, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg || !depth || !det || !box_table || !status || !ident || !keys_out || !rows_out)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "track_emit: null argument");
+    if (int rc = check_track_cfg(cfg)) return rc;
+    if (int rc = check_track_workspace(cfg, workspace, workspace_bytes)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::track_emit(*cfg, depth, det, box_table, reinterpret_cast<const int*>(status), reinterpret_cast<const int*>(ident),
+                          reinterpret_cast<unsigned long long*>(keys_out), reinterpret_cast<int*>(rows_out), workspace,
+                          static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_track_write(const vmapstep_track_cfg* cfg, const void* depth, const void* det, const float* box_table, const int32_t* status,
+                         const int32_t* ident, int32_t* labels_out, void* stream) {
+    if (!cfg || !depth || !det || !box_table || !status || !ident || !labels_out) return fail(VMAPSTEP_ERR_ARGUMENT, "track_write: null argument");
+    if (int rc = check_track_cfg(cfg)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::track_write(*cfg, depth, det, box_table, reinterpret_cast<const int*>(status), reinterpret_cast<const int*>(ident),
+                           reinterpret_cast<int*>(labels_out), static_cast<hipStream_t>(stream));
+}
+
 // ---- visibility culling ------------------------------------------------------------------------------------------------------------
 static int check_cull_cfg(const vmapstep_cull_cfg* cfg, const float* depth) {
     if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "cull: cfg is null");

@@ -11,7 +11,7 @@ With ``background_classes=()``, ``min_box=-1`` and ``sem=None`` the same call do
 (dataset.py:266-274) on a label image that ``box_filter`` has already merged - on the assumption that ``cv2.boundingRect`` over all
 external contours is the mask's min / max extent plus one, which could not be checked against OpenCV where this was written.
 ``box_filter`` itself is ``vmap_amd.instances.InstanceFilter.put``, whose ``labels`` go straight into this call.  Reading and decoding
-the image files, ScanNet's ``track_instance`` and the keyframe policy stay with the caller.
+the image files and the keyframe policy stay with the caller; ``track_instance`` is ``vmap_amd.tracking.InstanceTracker.put``.
 """
 from __future__ import annotations
 

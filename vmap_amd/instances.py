@@ -7,8 +7,8 @@ one full-frame pass per instance: ``cv2.erode``, Open3D's unprojection, ``voxel_
 and ``get_point_indices_within_bounding_box``.  ``InstanceFilter.put`` takes the frame as the image files hold it (row-major [H, W],
 after the caller's resize and edge crop) and keeps the state - a voxel-key set and a box table - on the device.  GPU only: there is
 no eager path.  ``res.labels`` is what ``box_filter`` returns; it goes to ``FrameIngest.put(rgb, depth, res.labels, None, t_wc,
-frame_id)`` on a ``FrameIngest`` built with ``background_classes=()``, ``min_box=-1``.  Reading files, resize, crop and the reference's
-``track_instance`` stay with the caller.
+frame_id)`` on a ``FrameIngest`` built with ``background_classes=()``, ``min_box=-1``.  Reading files, resize and crop stay with the caller; the reference's
+``track_instance`` is ``tracking.InstanceTracker``.
 
 One ``put``: filter_init, filter_stats, filter_decide, filter_count, filter_scan, filter_emit on the current stream with no host step
 between them, one host read of the table; torch's ``unique`` merges the frame's keys into the sorted state (the id is in a key's high
@@ -79,7 +79,47 @@ def box_row(box: BoundingBox, margin: float) -> np.ndarray:
     return row
 
 
-class InstanceFilter:
+class _KeyState:
+    """What ``InstanceFilter`` and ``tracking.InstanceTracker`` share: the stage events and the sorted key state (``device``, ``lib``,
+    ``voxel_size``, ``keys`` and a scratch ``_keys_buf`` are the subclass's)."""
+
+    # ---- stage timing: events on the stream, read on request ----
+    def _mark(self, name):
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(torch.cuda.current_stream(self.device))
+        self._events.setdefault(name, []).append(ev)
+
+    def stage_times(self) -> Dict[str, float]:
+        """Milliseconds of the last ``put`` per stage, from events on the stream (waits for the device): 'kernels' (stats, decide,
+        emit), 'read' (the host read of the table), 'sort_merge' (torch's unique and the segment lookup), 'search' (voxel_points
+        and the box search), 'write' (the label image and the box-table rows)."""
+        torch.cuda.synchronize(self.device)
+        return {k: float(v[0].elapsed_time(v[1])) for k, v in self._events.items() if len(v) == 2}
+
+    def _decode(self, keys, offsets_host):
+        """(points float32 [n, 3], bounds float32 [n_seg, 6]) of sorted keys in segments."""
+        n, n_seg = int(keys.numel()), len(offsets_host) - 1
+        points = torch.empty(n, 3, dtype=torch.float32, device=self.device)
+        bnd = torch.empty(n_seg, 6, dtype=torch.float32, device=self.device)
+        off = torch.from_numpy(np.ascontiguousarray(offsets_host, np.int64)).to(self.device)
+        keys = keys.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vmapstep_voxel_points(keys.data_ptr() if n else self._keys_buf.data_ptr(), n, off.data_ptr(), n_seg,
+                                                      self.voxel_size, points.data_ptr() if n else self._keys_buf.data_ptr(),
+                                                      bnd.data_ptr(), _devmem.stream(self.device)), self.lib)
+        return points, bnd
+
+    def _segment(self, keys, idv):
+        lo, hi = torch.searchsorted(keys, torch.tensor([idv << KEY_ID_SHIFT, (idv + 1) << KEY_ID_SHIFT], dtype=torch.int64, device=self.device)).tolist()
+        return keys[lo:hi]
+
+    def points(self, idv: int) -> torch.Tensor:
+        """The cloud of one id: device float32 [n, 3], the centres of its voxels in key order."""
+        seg = self._segment(self.keys, int(idv))
+        return self._decode(seg, [0, int(seg.numel())])[0]
+
+
+class InstanceFilter(_KeyState):
     """``InstanceFilter(width, height, intrinsics, depth_scale, max_depth, ...).put(depth, inst, sem, t_wc)``: one frame through
     ``box_filter``.  State: ``boxes`` {id: BoundingBox}, ``box_table`` (device float32 [max_ids, 16]), ``keys`` (sorted device int64)."""
 
@@ -125,41 +165,6 @@ class InstanceFilter:
         return _lib.FilterCfg(self.W, self.H, int(depth_f32), int(label_i32), self.depth_scale, self.max_depth, fx, fy, cx, cy, pose,
                               self.voxel_size, self.id_shift, self.min_pixels, self.min_points, self.erode_radius, self.max_ids,
                               len(self.background_classes), bg)
-
-    # ---- stage timing: events on the stream, read on request ----
-    def _mark(self, name):
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record(torch.cuda.current_stream(self.device))
-        self._events.setdefault(name, []).append(ev)
-
-    def stage_times(self) -> Dict[str, float]:
-        """Milliseconds of the last ``put`` per stage, from events on the stream (waits for the device): 'kernels' (stats, decide,
-        emit), 'read' (the host read of the table), 'sort_merge' (torch's unique and the segment lookup), 'search' (voxel_points
-        and the box search), 'write' (filter_write and the box-table rows)."""
-        torch.cuda.synchronize(self.device)
-        return {k: float(v[0].elapsed_time(v[1])) for k, v in self._events.items() if len(v) == 2}
-
-    def _decode(self, keys, offsets_host):
-        """(points float32 [n, 3], bounds float32 [n_seg, 6]) of sorted keys in segments."""
-        n, n_seg = int(keys.numel()), len(offsets_host) - 1
-        points = torch.empty(n, 3, dtype=torch.float32, device=self.device)
-        bnd = torch.empty(n_seg, 6, dtype=torch.float32, device=self.device)
-        off = torch.from_numpy(np.ascontiguousarray(offsets_host, np.int64)).to(self.device)
-        keys = keys.contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.vmapstep_voxel_points(keys.data_ptr() if n else self._keys_buf.data_ptr(), n, off.data_ptr(), n_seg,
-                                                      self.voxel_size, points.data_ptr() if n else self._keys_buf.data_ptr(),
-                                                      bnd.data_ptr(), _devmem.stream(self.device)), self.lib)
-        return points, bnd
-
-    def _segment(self, keys, idv):
-        lo, hi = torch.searchsorted(keys, torch.tensor([idv << KEY_ID_SHIFT, (idv + 1) << KEY_ID_SHIFT], dtype=torch.int64, device=self.device)).tolist()
-        return keys[lo:hi]
-
-    def points(self, idv: int) -> torch.Tensor:
-        """The cloud of one id: device float32 [n, 3], the centres of its voxels in key order."""
-        seg = self._segment(self.keys, int(idv))
-        return self._decode(seg, [0, int(seg.numel())])[0]
 
     def put(self, depth, inst, sem, t_wc) -> FilterResult:
         """One frame: depth u16 or f32 [H, W], inst and sem both u16 or both i32 [H, W], t_wc [4, 4] (camera to world).  Host tensors
