@@ -902,6 +902,68 @@ int vmapstep_raster_resolve(const uint64_t* keys, int64_t n_pixels, float* depth
                             int32_t* label, uint8_t* face_seen, void* stream);
 int vmapstep_depth_compare(const float* a, const float* b, int32_t n_views, int64_t pixels_per_view, int64_t* out, void* stream);
 
+/* ---- icp: the camera pose of a depth image by frame-to-model projective ICP ---------------------------------------------------------
+ * Every other section takes the camera-to-world pose as given (the reference reads it from the dataset, train.py:110).  This one
+ * finds it: a depth image (the SOURCE) is aligned to a depth image of the model (raster.rasterize of the reconstruction,
+ * render_view of the fields, or the previous frame) by point-to-plane ICP with projective association, coarse to fine.  The contract
+ * is this project's own; csrc/icp_rules.h is the definition, section by section (pyramid, maps, correspondence, the 29 quantised
+ * int64 sums, the LDL^T solve and the Cayley update, each with its order of operations), and tests/icp_oracle.py is written from it.
+ * Images are DEVICE float32 [width][height], width-major, as FrameStore holds them; both images share one camera and one size.
+ *
+ * A MAPS buffer (DEVICE, 16-byte aligned, vmapstep_icp_maps_bytes) holds the levels of one image, level 0 first: level l is W_l x
+ * H_l entries of four float32 (n0, n1, n2, d), W_0 = width, W_l+1 = ceil(W_l / 2); d = 0 marks an invalid pixel, n = (0, 0, 0) a pixel
+ * without a normal.  vmapstep_icp_pyramid fills it from a depth image: `levels` launches of icp_pyramid.
+ *
+ * vmapstep_icp_sums: ONE iteration's reduction at `level` under the pose t_sm (DEVICE float64 [12]: rows 0 .. 2 of the source-camera
+ * -> model-camera matrix) into sums (DEVICE int64 [29]; zeroed by the call): [0] inliers, [1 .. 21] the upper triangle of J J^T,
+ * [22 .. 27] J r, [28] r^2, each addend rint(x * 2^30).  Integer sums: bit-identical from call to call, whatever the grid.
+ *
+ * vmapstep_icp_track: the whole alignment.  pose (DEVICE float64 [12], in / out) starts as the initial estimate.  Levels run coarse
+ * first (levels - 1 .. 0), level l for iterations[l] iterations; an iteration is icp_reduce then icp_solve (one wave: LDL^T, the
+ * Cayley update pose <- dT . pose, the log rows, the sums back to zero).  Row i of the logs belongs to the i-th iteration in that
+ * order: log (DEVICE float64 [n][4]) = inlier count, sum of r^2, status, |x|^2; sums_log (DEVICE int64 [n][29]); pose_log (DEVICE
+ * float64 [n][12]) = the pose after the iteration.  Status: VMAPSTEP_ICP_OK; VMAPSTEP_ICP_DEGENERATE (count < min_inliers, a pivot
+ * <= pivot_rel * the largest diagonal entry, or a step that is not finite: the pose does not move); VMAPSTEP_ICP_SKIPPED (an earlier
+ * iteration of the level ended with |x|^2 < eps^2: the rest of the level returns at entry, its rows hold zero sums and the unchanged
+ * pose).  state: DEVICE, 256-byte aligned, VMAPSTEP_ICP_STATE_BYTES; the call zeroes it first.  A fixed chain of at most 2 * n
+ * launches on `stream`; nothing waits for the host.
+ *
+ * grid_cap is for tests: icp_reduce's grid is min(ceil(pixels / 256), 256), and a grid_cap in [1, 255] lowers the second 256.
+ *
+ * Refused before anything is enqueued: null arguments, levels outside [1, VMAPSTEP_ICP_MAX_LEVELS], level outside [0, levels), an
+ * iteration count outside [1, VMAPSTEP_ICP_MAX_ITERATIONS], a camera or a threshold that is not finite, fx or fy <= 0, min_depth < 0,
+ * max_depth <= min_depth, a negative band, dist_thresh, damping, pivot_rel, eps, min_inliers or grid_cap, a misaligned float64 / int64
+ * pointer (VMAPSTEP_ERR_ARGUMENT); width * height above VMAPSTEP_ICP_MAX_PIXELS - the bound under which the int64 sums cannot
+ * overflow, proven in csrc/icp_rules.h (VMAPSTEP_ERR_UNSUPPORTED); a maps buffer that is not 16-byte aligned or a state block that is
+ * not 256-byte aligned (VMAPSTEP_ERR_WORKSPACE). */
+#define VMAPSTEP_ICP_MAX_LEVELS 4
+#define VMAPSTEP_ICP_MAX_ITERATIONS 64
+#define VMAPSTEP_ICP_MAX_PIXELS 1048576
+#define VMAPSTEP_ICP_SUMS 29
+#define VMAPSTEP_ICP_LOG_COLS 4
+#define VMAPSTEP_ICP_STATE_BYTES 512
+#define VMAPSTEP_ICP_OK 0
+#define VMAPSTEP_ICP_DEGENERATE 1
+#define VMAPSTEP_ICP_SKIPPED 2
+typedef struct vmapstep_icp_cfg {
+    int32_t width, height, levels;
+    int32_t min_inliers;
+    int32_t iterations[VMAPSTEP_ICP_MAX_LEVELS];   /* per level, index 0 = the finest; vmapstep_icp_track alone reads them */
+    int32_t grid_cap;                              /* 0 = automatic */
+    int32_t reserved;
+    float fx, fy, cx, cy;                          /* of level 0 */
+    float min_depth, max_depth, band, dist_thresh, cos_thresh;
+    float reserved_f;
+    double damping, pivot_rel, eps;
+} vmapstep_icp_cfg;
+
+int vmapstep_icp_maps_bytes(const vmapstep_icp_cfg* cfg, size_t* bytes);
+int vmapstep_icp_pyramid(const vmapstep_icp_cfg* cfg, const float* depth, void* maps, void* stream);
+int vmapstep_icp_sums(const vmapstep_icp_cfg* cfg, const void* src_maps, const void* model_maps, int32_t level, const double* t_sm,
+                      int64_t* sums, void* stream);
+int vmapstep_icp_track(const vmapstep_icp_cfg* cfg, const void* src_maps, const void* model_maps, double* pose, double* log,
+                       int64_t* sums_log, double* pose_log, void* state, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

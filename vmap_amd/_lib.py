@@ -175,6 +175,25 @@ class RasterCfg(ctypes.Structure):
                 ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+class IcpCfg(ctypes.Structure):
+    """vmapstep_icp_cfg: the image size, the levels and their iteration counts, the camera and the thresholds of the vmapstep_icp_* calls."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("levels", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("iterations", ctypes.c_int32 * 4), ("grid_cap", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("band", ctypes.c_float), ("dist_thresh", ctypes.c_float),
+                ("cos_thresh", ctypes.c_float), ("reserved_f", ctypes.c_float),
+                ("damping", ctypes.c_double), ("pivot_rel", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+ICP_MAX_LEVELS = 4
+ICP_MAX_ITERATIONS = 64
+ICP_MAX_PIXELS = 1 << 20                   # the bound under which the int64 sums cannot overflow (csrc/icp_rules.h)
+ICP_SUMS = 29                              # inliers, 21 of J J^T, 6 of J r, r^2
+ICP_LOG_COLS = 4                           # inlier count, sum of r^2, status, |x|^2
+ICP_STATE_BYTES = 512
+ICP_OK, ICP_DEGENERATE, ICP_SKIPPED = 0, 1, 2
+
+
 EXPORTS = (
     "vmapstep_last_error", "vmapstep_abi_version", "vmapstep_param_layout", "vmapstep_workspace_bytes",
     "vmapstep_fwd_bwd", "vmapstep_render", "vmapstep_train_steps",
@@ -194,6 +213,7 @@ EXPORTS = (
     "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count", "vmapstep_cull_faces_emit",
     "vmapstep_components_workspace_bytes", "vmapstep_components_label", "vmapstep_components_stats",
     "vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve", "vmapstep_depth_compare",
+    "vmapstep_icp_maps_bytes", "vmapstep_icp_pyramid", "vmapstep_icp_sums", "vmapstep_icp_track",
 )
 
 _libs = {}
@@ -360,6 +380,14 @@ def load(path=None):
     lib.vmapstep_depth_compare.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     for fn in ("vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve",
                "vmapstep_depth_compare"):
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.vmapstep_icp_maps_bytes.argtypes = [ctypes.POINTER(IcpCfg), ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_icp_pyramid.argtypes = [ctypes.POINTER(IcpCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.vmapstep_icp_sums.argtypes = [ctypes.POINTER(IcpCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p]
+    lib.vmapstep_icp_track.argtypes = [ctypes.POINTER(IcpCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for fn in ("vmapstep_icp_maps_bytes", "vmapstep_icp_pyramid", "vmapstep_icp_sums", "vmapstep_icp_track"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
                "vmapstep_voxel_points", "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count",

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip, k_icp.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@ struct vmapstep_filter_cfg;
 struct vmapstep_track_cfg;
 struct vmapstep_cull_cfg;
 struct vmapstep_raster_cfg;
+struct vmapstep_icp_cfg;
 
 namespace vl {
 
@@ -169,5 +170,13 @@ int raster_draw(const vmapstep_raster_cfg& cfg, const float* vertices, long long
 int raster_resolve(const unsigned long long* keys, long long n_pixels, float* depth, int* face, const int* face_labels, long long n_faces, int* label,
                    unsigned char* face_seen, hipStream_t st);
 int depth_compare(const float* a, const float* b, int n_views, long long pixels, long long* out, hipStream_t st);
+
+// k_icp.hip: the depth tracker (icp_kernels.h).  A maps buffer is vl::icp_layout's.  icp_pyramid = one icp_pyramid launch per level;
+// icp_sums = sums to 0, one icp_reduce; icp_track = the state block to 0, then per level, coarse first, iterations[level] times
+// (icp_reduce, icp_solve): log [n_iter][4] float64, sums_log [n_iter][29] int64, pose_log [n_iter][12] float64, pose [12] float64 in / out.
+int icp_pyramid(const vmapstep_icp_cfg& cfg, const float* depth, void* maps, hipStream_t st);
+int icp_sums(const vmapstep_icp_cfg& cfg, const void* src_maps, const void* model_maps, int level, const double* t_sm, long long* sums, hipStream_t st);
+int icp_track(const vmapstep_icp_cfg& cfg, const void* src_maps, const void* model_maps, double* pose, double* log, long long* sums_log,
+              double* pose_log, void* state, hipStream_t st);
 
 }  // namespace vl

@@ -1,5 +1,5 @@
-// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, track, cull, component and raster families: the constants that both the kernels
-// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, track_kernels.h, cull_kernels.h, component_kernels.h, raster_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
+// launch_geometry.h - the launch geometry of the mesh, evaluation, bounds, view, ingest, filter, track, cull, component, raster and icp families: the constants that both the kernels
+// (mesh_kernels.h, eval_kernels.h, bounds_kernels.h, view_kernels.h, ingest_kernels.h, filter_kernels.h, track_kernels.h, cull_kernels.h, component_kernels.h, raster_kernels.h, icp_kernels.h) and the host-side workspace layouts and launch plans (launch.h) are built on.
 // constexpr values and host-side inline functions only, no device code and no HIP header: the C ABI unit sizes workspaces from them
 // without compiling anyone's kernels, and the CPU executor of tests/sim lays out its buffers by the same definitions.
 #pragma once
@@ -111,6 +111,20 @@ constexpr int kComparePer = 4;             // pixels per lane of depth_compare, 
 constexpr int kCompareBlock = kCompareWG * kComparePer;
 constexpr int kCompareInts = 4;            // a view's row: n_both, n_a_only, n_b_only, sum_q
 }  // namespace vr
+
+namespace vi {                             // the depth tracker (icp_kernels.h)
+constexpr int kMaxLevels = 4;
+constexpr int kTileW = 8;                  // icp_pyramid: a workgroup's tile of the output level, one pixel per lane; h is the fast axis
+constexpr int kTileH = 32;
+constexpr int kPyramidWG = kTileW * kTileH;
+constexpr int kReduceWG = 256;             // icp_reduce: four waves
+constexpr int kReduceGrid = 256;           // its grid at most: one workgroup per compute unit, whatever the image (measured: profiles/icp_bench.json)
+constexpr int kSolveWG = 64;               // icp_solve: one wave
+constexpr int kSums = 29;
+constexpr int kMaxIterations = 64;         // per level
+constexpr int kStateBytes = 512;           // the state block: the 29 sums (uint64) at 0, the level's finished flag (int32) at kFlagOffset
+constexpr int kFlagOffset = 256;
+}  // namespace vi
 
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
@@ -329,6 +343,25 @@ inline TrackLayout track_layout(int max_det, int max_pairs, int width, int heigh
     l.off_flags = l.off_pairs + ws_up((size_t)vf::kReplicas * max_pairs * sizeof(int));
     l.off_blk = l.off_flags + ws_up((size_t)width * height);
     l.bytes = l.off_blk + ws_up((size_t)filter_pix_blocks(width, height) * 2 * sizeof(int));
+    return l;
+}
+
+// Depth tracker.  A maps buffer holds every level's map, level 0 first: level l is W_l x H_l entries of four floats (n0, n1, n2, d),
+// width-major; W_l+1 = ceil(W_l / 2).  Offsets and the total are counted in entries of 16 bytes.
+struct IcpLayout {
+    int w[vi::kMaxLevels], h[vi::kMaxLevels];
+    long long off[vi::kMaxLevels];
+    long long entries;
+};
+inline IcpLayout icp_layout(int width, int height, int levels) {
+    IcpLayout l;
+    long long at = 0;
+    for (int k = 0; k < vi::kMaxLevels; ++k) {
+        l.w[k] = width; l.h[k] = height; l.off[k] = at;
+        if (k < levels) at += (long long)width * height;
+        width = (width + 1) / 2; height = (height + 1) / 2;
+    }
+    l.entries = at;
     return l;
 }
 

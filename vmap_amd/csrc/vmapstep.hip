@@ -1382,6 +1382,79 @@ int vmapstep_depth_compare(const float* a, const float* b, int32_t n_views, int6
     return vl::depth_compare(a, b, n_views, pixels_per_view, reinterpret_cast<long long*>(out), static_cast<hipStream_t>(stream));
 }
 
+// ---- depth tracker -----------------------------------------------------------------------------------------------------------------
+static int check_icp_cfg(const vmapstep_icp_cfg* cfg, bool track) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "icp: cfg is null");
+    if (cfg->width < 1 || cfg->height < 1 || cfg->levels < 1 || cfg->levels > VMAPSTEP_ICP_MAX_LEVELS || cfg->min_inliers < 0 || cfg->grid_cap < 0)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp: width=%d height=%d levels=%d (1 .. %d) min_inliers=%d grid_cap=%d", cfg->width, cfg->height,
+                    cfg->levels, VMAPSTEP_ICP_MAX_LEVELS, cfg->min_inliers, cfg->grid_cap);
+    const float cam[4] = {cfg->fx, cfg->fy, cfg->cx, cfg->cy};
+    for (float v : cam)
+        if (!std::isfinite(v)) return fail(VMAPSTEP_ERR_ARGUMENT, "icp: the camera must be finite");
+    if (!(cfg->fx > 0.0f && cfg->fy > 0.0f)) return fail(VMAPSTEP_ERR_ARGUMENT, "icp: fx and fy must be > 0");
+    if (!(cfg->min_depth >= 0.0f) || !std::isfinite(cfg->max_depth) || !(cfg->max_depth > cfg->min_depth))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp: 0 <= min_depth < max_depth < inf");
+    if (!(cfg->band >= 0.0f) || !std::isfinite(cfg->band) || !(cfg->dist_thresh >= 0.0f) || !std::isfinite(cfg->dist_thresh) || !std::isfinite(cfg->cos_thresh))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp: band and dist_thresh must be finite and >= 0, cos_thresh finite");
+    if (!(cfg->damping >= 0.0) || !std::isfinite(cfg->damping) || !(cfg->pivot_rel >= 0.0) || !std::isfinite(cfg->pivot_rel) || !(cfg->eps >= 0.0) ||
+        !std::isfinite(cfg->eps))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp: damping, pivot_rel and eps must be finite and >= 0");
+    if (track)
+        for (int l = 0; l < cfg->levels; ++l)
+            if (cfg->iterations[l] < 1 || cfg->iterations[l] > VMAPSTEP_ICP_MAX_ITERATIONS)
+                return fail(VMAPSTEP_ERR_ARGUMENT, "icp: iterations[%d]=%d (1 .. %d)", l, cfg->iterations[l], VMAPSTEP_ICP_MAX_ITERATIONS);
+    if ((long long)cfg->width * cfg->height > VMAPSTEP_ICP_MAX_PIXELS)
+        return fail(VMAPSTEP_ERR_UNSUPPORTED, "icp limits: width * height <= %d, the bound under which the integer sums cannot overflow (width=%d height=%d)",
+                    VMAPSTEP_ICP_MAX_PIXELS, cfg->width, cfg->height);
+    return VMAPSTEP_OK;
+}
+
+static int check_icp_maps(const void* maps, const char* what) {
+    if (!maps) return fail(VMAPSTEP_ERR_ARGUMENT, "icp: %s is null", what);
+    if (reinterpret_cast<uintptr_t>(maps) % 16) return fail(VMAPSTEP_ERR_WORKSPACE, "icp: %s must be 16-byte aligned", what);
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_icp_maps_bytes(const vmapstep_icp_cfg* cfg, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "bytes is null");
+    if (int rc = check_icp_cfg(cfg, false)) return rc;
+    *bytes = (size_t)vl::icp_layout(cfg->width, cfg->height, cfg->levels).entries * 16;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_icp_pyramid(const vmapstep_icp_cfg* cfg, const float* depth, void* maps, void* stream) {
+    if (int rc = check_icp_cfg(cfg, false)) return rc;
+    if (!depth || reinterpret_cast<uintptr_t>(depth) % 4) return fail(VMAPSTEP_ERR_ARGUMENT, "icp_pyramid: depth is null or misaligned");
+    if (int rc = check_icp_maps(maps, "maps")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::icp_pyramid(*cfg, depth, maps, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_icp_sums(const vmapstep_icp_cfg* cfg, const void* src_maps, const void* model_maps, int32_t level, const double* t_sm,
+                      int64_t* sums, void* stream) {
+    if (int rc = check_icp_cfg(cfg, false)) return rc;
+    if (level < 0 || level >= cfg->levels) return fail(VMAPSTEP_ERR_ARGUMENT, "icp_sums: level=%d (levels=%d)", level, cfg->levels);
+    if (!t_sm || !sums || (reinterpret_cast<uintptr_t>(t_sm) | reinterpret_cast<uintptr_t>(sums)) % 8)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp_sums: t_sm or sums is null or misaligned");
+    if (int rc = check_icp_maps(src_maps, "src_maps")) return rc;
+    if (int rc = check_icp_maps(model_maps, "model_maps")) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::icp_sums(*cfg, src_maps, model_maps, level, t_sm, reinterpret_cast<long long*>(sums), static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_icp_track(const vmapstep_icp_cfg* cfg, const void* src_maps, const void* model_maps, double* pose, double* log,
+                       int64_t* sums_log, double* pose_log, void* state, void* stream) {
+    if (int rc = check_icp_cfg(cfg, true)) return rc;
+    if (!pose || !log || !sums_log || !pose_log ||
+        (reinterpret_cast<uintptr_t>(pose) | reinterpret_cast<uintptr_t>(log) | reinterpret_cast<uintptr_t>(sums_log) | reinterpret_cast<uintptr_t>(pose_log)) % 8)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "icp_track: pose, log, sums_log or pose_log is null or misaligned");
+    if (int rc = check_icp_maps(src_maps, "src_maps")) return rc;
+    if (int rc = check_icp_maps(model_maps, "model_maps")) return rc;
+    if (!state || reinterpret_cast<uintptr_t>(state) % kAlign) return fail(VMAPSTEP_ERR_WORKSPACE, "icp_track: state must be 256-byte aligned");
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::icp_track(*cfg, src_maps, model_maps, pose, log, reinterpret_cast<long long*>(sums_log), pose_log, state, static_cast<hipStream_t>(stream));
+}
+
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {
     if (!bytes || n_obj < 1) return fail(VMAPSTEP_ERR_ARGUMENT, "null / non-positive argument");
     *bytes = align_up((size_t)n_obj * sizeof(int));

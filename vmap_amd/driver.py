@@ -206,6 +206,16 @@ class HipMapper:
                                     None if background_center is None else [background_center], background_samples)]
         return render.render_view_groups(groups, t_wc, intrinsics, width, height, **kw)
 
+    def track_pose(self, depth, t_wc_init, boxes, intrinsics, *, min_opacity=0.5, iterations=(10, 5, 4), render_kw=None, **cfg):
+        """The camera-to-world pose of the depth image ``depth`` ([W, H]) against the map: ``render_view(boxes, t_wc_init, ...)``
+        (``render_kw``: its keywords - centers, samples, background_box ...) is the model, its depth zeroed where the opacity is below
+        ``min_opacity``, and ``odometry.DepthTracker.track_to_view`` aligns the frame to it.  -> ``odometry.TrackedPose``; ``cfg``:
+        ``odometry.track_depth``'s keyword arguments.  This is the call that replaces an outside SLAM system's pose for the frame."""
+        from . import odometry
+        width, height = (int(s) for s in depth.shape)
+        view = self.render_view(boxes, t_wc_init, intrinsics, width, height, **(render_kw or {}))
+        return odometry.DepthTracker(intrinsics, width, height, iterations, **cfg).track_to_view(view, depth, min_opacity, t_wc=t_wc_init)
+
     def check_flags(self, res: step.StepResult):
         """Host-side look at the device flags of a frame (the reference exits on 'loss explode', render_rays.py:88-90)."""
         f = res.flags.cpu()

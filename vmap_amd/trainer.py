@@ -89,6 +89,16 @@ class Trainer:
         from . import render
         return render.render_view([self], [bound], t_wc, intrinsics, width, height, centers=[obj_center], **kw)
 
+    @torch.no_grad()
+    def track_pose(self, depth, t_wc_init, bound, obj_center, intrinsics, *, min_opacity=0.5, samples=16, iterations=(10, 5, 4), **cfg):
+        """The camera-to-world pose of the depth image ``depth`` ([W, H]) against this object's field: ``render_view`` from
+        ``t_wc_init`` is the model (depth zeroed where the opacity is below ``min_opacity``), ``odometry.DepthTracker.track_to_view``
+        aligns the frame to it.  -> ``odometry.TrackedPose``; ``cfg``: ``odometry.track_depth``'s keyword arguments.  GPU only."""
+        from . import odometry
+        width, height = (int(s) for s in depth.shape)
+        view = self.render_view(bound, obj_center, t_wc_init, intrinsics, width, height, samples=samples)
+        return odometry.DepthTracker(intrinsics, width, height, iterations, **cfg).track_to_view(view, depth, min_opacity, t_wc=t_wc_init)
+
     def _eval_points_hip(self, points: torch.Tensor):
         import ctypes
         from . import _lib
