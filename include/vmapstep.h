@@ -339,6 +339,19 @@ int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, 
                        float* vertices, float* normals, int32_t* faces, int64_t n_vertices, int64_t n_faces,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* Marching cubes over the observed part of a volume: `valid` (DEVICE uint8 [nx*ny*nz], non-zero = the point holds a value; NULL = every
+ * point, the two entries above).  A cell exists iff all eight of its corners are valid; faces come from existing cells only; the crossing
+ * on a grid edge becomes a vertex iff at least one of the up to four cells around the edge exists, so no vertex is left unreferenced; the
+ * normal's stencil treats an invalid neighbour like the grid border (one-sided; 0 along an axis with neither side valid).  The values of
+ * invalid points are never compared or interpolated into the output.  With `valid` all non-zero the output equals the unmasked call's bit
+ * for bit, in the same order.  Same workspace, limits and order as above.  edge_ids (DEVICE int32 [n_vertices], may be NULL) receives
+ * owning point * 3 + axis of every vertex: the two grid points a vertex lies between, for callers that interpolate other volumes. */
+int vmapstep_mesh_count_valid(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int vmapstep_mesh_emit_valid(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                             const float affine[12], float* vertices, float* normals, int32_t* faces, int32_t* edge_ids,
+                             int64_t n_vertices, int64_t n_faces, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mesh evaluation (the reference's metric/eval_3D_obj.py:8-41 and metric/metrics.py: crop, sample, nearest neighbours) -------------
  * Point sets are CSR-segmented: every call takes the offsets [n_sets + 1] (int64) twice, as a DEVICE array the kernels read and
  * as a HOST array the library validates and plans the launch from (the two must hold the same values).  Offsets must be
@@ -963,6 +976,49 @@ int vmapstep_icp_sums(const vmapstep_icp_cfg* cfg, const void* src_maps, const v
                       int64_t* sums, void* stream);
 int vmapstep_icp_track(const vmapstep_icp_cfg* cfg, const void* src_maps, const void* model_maps, double* pose, double* log,
                        int64_t* sums_log, double* pose_log, void* state, void* stream);
+
+/* ---- TSDF fusion: posed depth frames into a truncated signed distance volume and a colour volume -------------------------------------
+ * The baseline the paper compares its object fields against (TSDF-Fusion), for the whole scene or masked to one object.  The contract
+ * below is this project's own (csrc/tsdf_rules.h is the definition); float32 throughout, every fma ONE fused operation, every other
+ * operation rounded on its own, IEEE division.
+ *
+ * Volume: tsdf, weight (DEVICE float32 [nx][ny][nz], C order) and optionally color (DEVICE float32 [nx*ny*nz][4]: r, g, b on the
+ * 0..255 scale and the colour's own weight wc; 16-byte aligned).  All are read AND written; an empty volume is all zeros.  Voxel
+ * (i, j, k) lies at p_r = fma(A[4r+2], k, fma(A[4r+1], j, fma(A[4r], i, A[4r+3]))) with A = cfg.affine (rows [A | b], index -> world):
+ * vmapstep_mesh_grid_points' arithmetic, bit for bit.
+ *
+ * Frames: the cull section's (depth, t_wc, slots, the 64-bit image offset), plus rgbx (DEVICE uint8 [slots][width][height][4], byte 3
+ * unused) and inst (DEVICE int32 [slots][width][height]).  Per voxel and frame, in the order the frames are given:
+ *   (w, h, z) = the cull section's projection of p (z > min_depth, half-to-even pixel, margin); a failure means no update;
+ *   d = depth[slot][w][h], usable iff d > min_depth && d <= max_depth (NaN, inf, 0 and negatives fail);
+ *   with obj_id >= 0 only where inst[slot][w][h] == obj_id (obj_id < 0: inst is not read and may be NULL);
+ *   sdf = d - z (one rounded subtraction); no update unless sdf >= -trunc;
+ *   s = fminf(1, sdf / trunc);  W1 = W + 1;  D <- fma(D, W, s) / W1;  W <- fminf(W1, max_weight);
+ *   colour only where sdf <= trunc: wc1 = wc + 1;  c <- fma(c, wc, (float)byte) / wc1 per channel;  wc <- fminf(wc1, max_weight).
+ * An all-zero pose (an unused slot) gives z = 0 and updates nothing.  A voxel is owned by one lane and updated sequentially, without
+ * atomics: the result depends on the frame order alone, and one call over frames 0..K equals a call over 0..a followed by one over a..K
+ * bit for bit.  A voxel no frame updated keeps its bits (it is either not written or written back as loaded).
+ *
+ * Everything is enqueued on `stream`, nothing waits; n_frames == 0 is VMAPSTEP_OK and writes nothing.  Before anything is enqueued:
+ * VMAPSTEP_ERR_ARGUMENT for a null cfg, tsdf, weight, depth or poses; a pointer that is not aligned to its element (color: 16 bytes);
+ * color without rgbx; obj_id >= 0 without inst; trunc not > 0 or not finite; max_weight not >= 1; max_depth not > min_depth; the
+ * cull section's conditions on width, height, margin, min_depth and the camera; n_frames < 0; an affine that is not finite.
+ * VMAPSTEP_ERR_UNSUPPORTED for a volume outside the mesh section's limits (each side 2..1024, 3*nx*ny*nz < 2^31). */
+typedef struct vmapstep_tsdf_cfg {
+    int32_t nx, ny, nz;
+    int32_t obj_id;                /* < 0: every pixel */
+    float affine[12];              /* voxel index -> world, rows [A | b] */
+    float fx, fy, cx, cy;
+    int32_t width, height;
+    int32_t margin;                /* pixels at the border that do not count */
+    int32_t reserved;              /* 0 */
+    float min_depth, max_depth;    /* a measurement d is usable iff min_depth < d <= max_depth; min_depth >= 0 */
+    float trunc;                   /* metres, > 0 */
+    float max_weight;              /* >= 1 */
+} vmapstep_tsdf_cfg;
+
+int vmapstep_tsdf_integrate(const vmapstep_tsdf_cfg* cfg, float* tsdf, float* weight, float* color, const float* depth, const uint8_t* rgbx,
+                            const int32_t* inst, const float* poses, const int32_t* slots, int32_t n_frames, void* stream);
 
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:

@@ -6,4 +6,4 @@ does, and raises if it is missing - there is no CPU or eager-PyTorch fallback fo
 """
 from . import layout  # noqa: F401
 
-__all__ = ["layout", "synth", "fields", "trainer", "ensemble", "step", "visibility", "components", "raster", "odometry"]
+__all__ = ["layout", "synth", "fields", "trainer", "ensemble", "step", "visibility", "components", "raster", "odometry", "tsdf"]

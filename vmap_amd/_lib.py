@@ -185,6 +185,15 @@ class IcpCfg(ctypes.Structure):
                 ("damping", ctypes.c_double), ("pivot_rel", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
+class TsdfCfg(ctypes.Structure):
+    """vmapstep_tsdf_cfg: the volume's shape and affine, the object id, the camera, the image size and the rules of vmapstep_tsdf_integrate."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("obj_id", ctypes.c_int32),
+                ("affine", ctypes.c_float * 12),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("margin", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("trunc", ctypes.c_float), ("max_weight", ctypes.c_float)]
+
+
 ICP_MAX_LEVELS = 4
 ICP_MAX_ITERATIONS = 64
 ICP_MAX_PIXELS = 1 << 20                   # the bound under which the int64 sums cannot overflow (csrc/icp_rules.h)
@@ -214,6 +223,7 @@ EXPORTS = (
     "vmapstep_components_workspace_bytes", "vmapstep_components_label", "vmapstep_components_stats",
     "vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve", "vmapstep_depth_compare",
     "vmapstep_icp_maps_bytes", "vmapstep_icp_pyramid", "vmapstep_icp_sums", "vmapstep_icp_track",
+    "vmapstep_mesh_count_valid", "vmapstep_mesh_emit_valid", "vmapstep_tsdf_integrate",
 )
 
 _libs = {}
@@ -388,6 +398,14 @@ def load(path=None):
     lib.vmapstep_icp_track.argtypes = [ctypes.POINTER(IcpCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     for fn in ("vmapstep_icp_maps_bytes", "vmapstep_icp_pyramid", "vmapstep_icp_sums", "vmapstep_icp_track"):
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.vmapstep_mesh_count_valid.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_mesh_emit_valid.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                             ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.vmapstep_tsdf_integrate.argtypes = [ctypes.POINTER(TsdfCfg)] + [ctypes.c_void_p] * 8 + [ctypes.c_int32, ctypes.c_void_p]
+    for fn in ("vmapstep_mesh_count_valid", "vmapstep_mesh_emit_valid", "vmapstep_tsdf_integrate"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
                "vmapstep_voxel_points", "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count",

@@ -27,8 +27,10 @@ int mesh_grid_points(int nx, int ny, int nz, const float affine[12], float* poin
     return launched("mesh_grid_points");
 }
 
-int mesh_count(const float* volume, int nx, int ny, int nz, float level, long long* counts, void* workspace, hipStream_t st) {
+int mesh_count(const float* volume, const unsigned char* valid, int nx, int ny, int nz, float level, long long* counts, void* workspace,
+               hipStream_t st) {
     vm::MeshArgs a = mesh_args(volume, nx, ny, nz, level, workspace);
+    a.valid = valid;
     a.counts = counts;
     hipLaunchKernelGGL(vm::mesh_count, dim3(a.nblk), dim3(vm::kMeshWG), 0, st, a);
     if (int rc = launched("mesh_count")) return rc;
@@ -36,9 +38,11 @@ int mesh_count(const float* volume, int nx, int ny, int nz, float level, long lo
     return launched("mesh_scan");
 }
 
-int mesh_emit(const float* volume, int nx, int ny, int nz, float level, const float* affine, const float* ninv, float* vertices,
-              float* normals, int* faces, long long n_vertices, long long n_faces, void* workspace, hipStream_t st) {
+int mesh_emit(const float* volume, const unsigned char* valid, int nx, int ny, int nz, float level, const float* affine, const float* ninv,
+              float* vertices, float* normals, int* faces, int* edge_ids, long long n_vertices, long long n_faces, void* workspace,
+              hipStream_t st) {
     vm::MeshArgs a = mesh_args(volume, nx, ny, nz, level, workspace);
+    a.valid = valid; a.edge_ids = edge_ids;
     a.verts = vertices; a.normals = normals; a.faces = faces; a.n_vertices = n_vertices; a.n_faces = n_faces;
     if (affine) {
         std::memcpy(a.A, affine, sizeof(a.A));

@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip, k_icp.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip, k_icp.hip, k_tsdf.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@ struct vmapstep_track_cfg;
 struct vmapstep_cull_cfg;
 struct vmapstep_raster_cfg;
 struct vmapstep_icp_cfg;
+struct vmapstep_tsdf_cfg;
 
 namespace vl {
 
@@ -71,10 +72,14 @@ int view_field(const vk::StepArgs& pack, const vv::ViewArgs& a, long long entrie
 // k_mesh.hip: marching cubes (mesh_kernels.h) and the dense grid Trainer.meshing queries.  The workspace of a [nx][ny][nz] volume:
 // per-workgroup (vertices, faces) int64 pairs, then the first vertex id (int32) and the crossing-edge mask (uint8) of every point.
 int mesh_grid_points(int nx, int ny, int nz, const float affine[12], float* points, hipStream_t st);
-int mesh_count(const float* volume, int nx, int ny, int nz, float level, long long* counts, void* workspace, hipStream_t st);
+// valid: null = no mask; otherwise [n] bytes, non-zero = the point holds a value (cells with an invalid corner do not exist)
+int mesh_count(const float* volume, const unsigned char* valid, int nx, int ny, int nz, float level, long long* counts, void* workspace,
+               hipStream_t st);
 // affine / ninv: null = index space; otherwise [A | b] rows and the inverse transpose of A (rows, for the normals)
-int mesh_emit(const float* volume, int nx, int ny, int nz, float level, const float* affine, const float* ninv, float* vertices,
-              float* normals, int* faces, long long n_vertices, long long n_faces, void* workspace, hipStream_t st);
+// edge_ids: null, or [n_vertices] int32 = owning point * 3 + axis of every vertex
+int mesh_emit(const float* volume, const unsigned char* valid, int nx, int ny, int nz, float level, const float* affine, const float* ninv,
+              float* vertices, float* normals, int* faces, int* edge_ids, long long n_vertices, long long n_faces, void* workspace,
+              hipStream_t st);
 
 // k_eval.hip: mesh evaluation (eval_kernels.h).  Nearest neighbours: the workspace holds the per-set prefix of the work items
 // (int64 [n_sets + 1]) and one packed (squared distance, index) key per query (uint64 [n_queries]).
@@ -178,5 +183,10 @@ int icp_pyramid(const vmapstep_icp_cfg& cfg, const float* depth, void* maps, hip
 int icp_sums(const vmapstep_icp_cfg& cfg, const void* src_maps, const void* model_maps, int level, const double* t_sm, long long* sums, hipStream_t st);
 int icp_track(const vmapstep_icp_cfg& cfg, const void* src_maps, const void* model_maps, double* pose, double* log, long long* sums_log,
               double* pose_log, void* state, hipStream_t st);
+
+// k_tsdf.hip: TSDF fusion (tsdf_kernels.h): one tsdf_integrate launch over all n_frames; color / rgbx / inst may be null (the C ABI has
+// checked that what cfg makes the kernel read is there)
+int tsdf_integrate(const vmapstep_tsdf_cfg& cfg, float* tsdf, float* weight, float* color, const float* depth, const unsigned char* rgbx,
+                   const int* inst, const float* t_wc, const int* slots, int n_frames, hipStream_t st);
 
 }  // namespace vl

@@ -126,6 +126,13 @@ constexpr int kStateBytes = 512;           // the state block: the 29 sums (uint
 constexpr int kFlagOffset = 256;
 }  // namespace vi
 
+namespace vtsdf {                          // TSDF fusion (tsdf_kernels.h)
+constexpr int kTsdfWG = 256;               // tsdf_integrate: four waves
+constexpr int kVoxelsPer = 4;              // voxels per lane, kTsdfWG apart (a wave's 64 voxels are consecutive along k)
+constexpr int kTsdfTile = kTsdfWG * kVoxelsPer;   // voxels per workgroup
+constexpr int kTsdfChunk = 32;             // frames whose poses and image offsets a workgroup stages in LDS at a time
+}  // namespace vtsdf
+
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
 

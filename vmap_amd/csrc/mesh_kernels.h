@@ -321,6 +321,8 @@ struct MeshArgs {
     float A[12];                       // output affine, rows [A | b] (has_affine), applied to the index-space vertex
     float Ninv[9];                     // inverse transpose of A's linear part (rows), for the normals
     int has_affine;
+    const unsigned char* valid;        // [n] non-zero = the point holds a value; null (a zero-filled MeshArgs) = no mask
+    int* edge_ids;                     // [n_vertices] owning point * 3 + axis of every vertex; may be null
 };
 
 __device__ __forceinline__ void decode(int p, const MeshArgs& a, int& i, int& j, int& k) {
@@ -351,6 +353,35 @@ __device__ __forceinline__ bool owns_cell(const MeshArgs& a, int i, int j, int k
     return i + 1 < a.nx && j + 1 < a.ny && k + 1 < a.nz;
 }
 
+// The mask (a.valid != null).  A cell exists iff, besides, all eight corners are valid; faces come from existing cells only; the
+// crossing on a grid edge becomes a vertex iff at least one of the up to four cells around the edge exists, so that no vertex is left
+// unreferenced.  With every point valid all of this is the unmasked rule (every side of the grid is >= 2: an edge always has a cell).
+__device__ __forceinline__ bool corners_valid(const MeshArgs& a, int p) {
+    const int si = a.ny * a.nz, sj = a.nz;
+    const unsigned char* v = a.valid + p;
+    return v[0] && v[1] && v[sj + 1] && v[sj] && v[si] && v[si + 1] && v[si + sj + 1] && v[si + sj];
+}
+
+__device__ __forceinline__ bool cell_exists(const MeshArgs& a, int p, int i, int j, int k) {
+    return owns_cell(a, i, j, k) && (!a.valid || corners_valid(a, p));
+}
+
+// whether a cell around the +axis-ax edge of point p = (idx) exists: the cells whose lowest corner is p less 0 or 1 along each of the
+// two other axes
+__device__ __forceinline__ bool edge_has_cell(const MeshArgs& a, int p, const int idx[3], int ax) {
+    const int stride[3] = {a.ny * a.nz, a.nz, 1};
+    const int u = (ax + 1) % 3, w = (ax + 2) % 3;
+    for (int bu = 0; bu < 2; ++bu)
+        for (int bw = 0; bw < 2; ++bw) {
+            int c[3] = {idx[0], idx[1], idx[2]};
+            c[u] -= bu;
+            c[w] -= bw;
+            if (c[u] < 0 || c[w] < 0) continue;
+            if (cell_exists(a, p - bu * stride[u] - bw * stride[w], c[0], c[1], c[2])) return true;
+        }
+    return false;
+}
+
 __global__ __launch_bounds__(kMeshWG) void mesh_count(const MeshArgs a) {
     __shared__ int lds4[2][kMeshWG / 64];
     const int p = blockIdx.x * kMeshWG + threadIdx.x;
@@ -364,9 +395,15 @@ __global__ __launch_bounds__(kMeshWG) void mesh_count(const MeshArgs a) {
         if (i + 1 < a.nx) m |= (unsigned)((v[a.ny * a.nz] > a.level) != up);
         if (j + 1 < a.ny) m |= (unsigned)((v[a.nz] > a.level) != up) << 1;
         if (k + 1 < a.nz) m |= (unsigned)((v[1] > a.level) != up) << 2;
+        if (a.valid && m) {            // crossings are sparse: the cells around an edge are looked at for those only
+            const int idx[3] = {i, j, k};
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax)
+                if ((m >> ax & 1u) && !edge_has_cell(a, p, idx, ax)) m &= ~(1u << ax);
+        }
         a.emask[p] = (unsigned char)m;
         nv = __popc(m);
-        if (owns_cell(a, i, j, k)) nf = tri_count(cube_index(a, p));
+        if (cell_exists(a, p, i, j, k)) nf = tri_count(cube_index(a, p));
     }
     int tv, tf;                        // two scans in a row: an LDS array each (scan_ops.h's barrier contract)
     vscan::wg_exclusive_scan<kMeshWG>(nv, lds4[0], tv);
@@ -394,13 +431,20 @@ __global__ __launch_bounds__(kScanWG) void mesh_scan(const MeshArgs a) {
     }
 }
 
-// numpy.gradient's stencil of the volume at point (i, j, k): central differences inside, one-sided (first order) at the borders
+// numpy.gradient's stencil of the volume at point (i, j, k): central differences inside, one-sided (first order) at the borders.
+// An invalid neighbour counts as the border; with neither side valid the component is 0 (without a mask every side of the grid is
+// >= 2, so one side always exists).
+__device__ __forceinline__ float grad_axis(const MeshArgs& a, int p, int at, int dim, int s) {
+    const float* v = a.vol + p;
+    const bool lo = at > 0 && (!a.valid || a.valid[p - s]), hi = at < dim - 1 && (!a.valid || a.valid[p + s]);
+    return lo && hi ? (v[s] - v[-s]) * 0.5f : hi ? v[s] - v[0] : lo ? v[0] - v[-s] : 0.0f;
+}
+
 __device__ __forceinline__ void grad_at(const MeshArgs& a, int i, int j, int k, float g[3]) {
-    const int si = a.ny * a.nz, sj = a.nz;
-    const float* v = a.vol + (i * a.ny + j) * a.nz + k;
-    g[0] = i == 0 ? v[si] - v[0] : i == a.nx - 1 ? v[0] - v[-si] : (v[si] - v[-si]) * 0.5f;
-    g[1] = j == 0 ? v[sj] - v[0] : j == a.ny - 1 ? v[0] - v[-sj] : (v[sj] - v[-sj]) * 0.5f;
-    g[2] = k == 0 ? v[1] - v[0] : k == a.nz - 1 ? v[0] - v[-1] : (v[1] - v[-1]) * 0.5f;
+    const int p = (i * a.ny + j) * a.nz + k;
+    g[0] = grad_axis(a, p, i, a.nx, a.ny * a.nz);
+    g[1] = grad_axis(a, p, j, a.ny, a.nz);
+    g[2] = grad_axis(a, p, k, a.nz, 1);
 }
 
 __global__ __launch_bounds__(kMeshWG) void mesh_emit_vertices(const MeshArgs a) {
@@ -427,6 +471,7 @@ __global__ __launch_bounds__(kMeshWG) void mesh_emit_vertices(const MeshArgs a) 
         float pos[3] = {(float)idx[0], (float)idx[1], (float)idx[2]};
         pos[ax] += t;
         if (vid < a.n_vertices) {
+            if (a.edge_ids) a.edge_ids[vid] = 3 * p + ax;
             float* out = a.verts + 3 * vid;
             if (a.has_affine) {
 #pragma unroll
@@ -464,7 +509,7 @@ __global__ __launch_bounds__(kMeshWG) void mesh_emit_faces(const MeshArgs a) {
     if (p < a.n) {
         int i, j, k;
         decode(p, a, i, j, k);
-        if (owns_cell(a, i, j, k)) {
+        if (cell_exists(a, p, i, j, k)) {
             cube = cube_index(a, p);
             nt = tri_count(cube);
         }

@@ -567,18 +567,30 @@ int vmapstep_mesh_grid_points(int32_t nx, int32_t ny, int32_t nz, const float af
     return vl::mesh_grid_points(nx, ny, nz, affine, points, static_cast<hipStream_t>(stream));
 }
 
-int vmapstep_mesh_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+int vmapstep_mesh_count_valid(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream) {
     if (!volume || !counts) return fail(VMAPSTEP_ERR_ARGUMENT, "null argument");
     if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
     if (int rc = check_mesh_workspace(nx, ny, nz, workspace, workspace_bytes)) return rc;
     VMAPSTEP_ON_STREAM_DEVICE(stream);
-    return vl::mesh_count(volume, nx, ny, nz, level, reinterpret_cast<long long*>(counts), workspace, static_cast<hipStream_t>(stream));
+    return vl::mesh_count(volume, valid, nx, ny, nz, level, reinterpret_cast<long long*>(counts), workspace, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_mesh_count(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* counts,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    return vmapstep_mesh_count_valid(volume, nullptr, nx, ny, nz, level, counts, workspace, workspace_bytes, stream);
 }
 
 int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, float level, const float affine[12],
                        float* vertices, float* normals, int32_t* faces, int64_t n_vertices, int64_t n_faces,
                        void* workspace, size_t workspace_bytes, void* stream) {
+    return vmapstep_mesh_emit_valid(volume, nullptr, nx, ny, nz, level, affine, vertices, normals, faces, nullptr, n_vertices, n_faces,
+                                    workspace, workspace_bytes, stream);
+}
+
+int vmapstep_mesh_emit_valid(const float* volume, const uint8_t* valid, int32_t nx, int32_t ny, int32_t nz, float level,
+                             const float affine[12], float* vertices, float* normals, int32_t* faces, int32_t* edge_ids,
+                             int64_t n_vertices, int64_t n_faces, void* workspace, size_t workspace_bytes, void* stream) {
     if (!volume || n_vertices < 0 || n_faces < 0 || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces))
         return fail(VMAPSTEP_ERR_ARGUMENT, "null argument / negative count");
     if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
@@ -599,7 +611,7 @@ int vmapstep_mesh_emit(const float* volume, int32_t nx, int32_t ny, int32_t nz, 
     }
     if (n_vertices == 0 && n_faces == 0) return VMAPSTEP_OK;
     VMAPSTEP_ON_STREAM_DEVICE(stream);
-    return vl::mesh_emit(volume, nx, ny, nz, level, affine, affine ? ninv : nullptr, vertices, normals, faces, n_vertices, n_faces,
+    return vl::mesh_emit(volume, valid, nx, ny, nz, level, affine, affine ? ninv : nullptr, vertices, normals, faces, edge_ids, n_vertices, n_faces,
                          workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -1453,6 +1465,34 @@ int vmapstep_icp_track(const vmapstep_icp_cfg* cfg, const void* src_maps, const 
     if (!state || reinterpret_cast<uintptr_t>(state) % kAlign) return fail(VMAPSTEP_ERR_WORKSPACE, "icp_track: state must be 256-byte aligned");
     VMAPSTEP_ON_STREAM_DEVICE(stream);
     return vl::icp_track(*cfg, src_maps, model_maps, pose, log, reinterpret_cast<long long*>(sums_log), pose_log, state, static_cast<hipStream_t>(stream));
+}
+
+// ---- TSDF fusion -------------------------------------------------------------------------------------------------------------------
+int vmapstep_tsdf_integrate(const vmapstep_tsdf_cfg* cfg, float* tsdf, float* weight, float* color, const float* depth, const uint8_t* rgbx,
+                            const int32_t* inst, const float* poses, const int32_t* slots, int32_t n_frames, void* stream) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: cfg is null");
+    if (!tsdf || !weight || !depth || !poses) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: tsdf, weight, depth or poses is null");
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((at(tsdf) | at(weight) | at(depth) | at(poses) | at(inst) | at(slots) | at(rgbx)) % 4 || at(color) % 16)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: a pointer is not aligned to its element (color: 16 bytes)");
+    if (color && !rgbx) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: a colour volume needs rgbx");
+    if (cfg->obj_id >= 0 && !inst) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: obj_id=%d needs inst", cfg->obj_id);
+    if (!(cfg->trunc > 0.0f) || !std::isfinite(cfg->trunc)) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: trunc must be finite and > 0");
+    if (!(cfg->max_weight >= 1.0f)) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: max_weight must be >= 1");
+    if (!(cfg->max_depth > cfg->min_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: max_depth must be > min_depth");
+    if (n_frames < 0) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: n_frames=%d", n_frames);
+    for (int e = 0; e < 12; ++e)
+        if (!std::isfinite(cfg->affine[e])) return fail(VMAPSTEP_ERR_ARGUMENT, "tsdf: the affine is not finite");
+    vmapstep_cull_cfg cam;
+    std::memset(&cam, 0, sizeof(cam));
+    cam.fx = cfg->fx; cam.fy = cfg->fy; cam.cx = cfg->cx; cam.cy = cfg->cy; cam.min_depth = cfg->min_depth;
+    cam.width = cfg->width; cam.height = cfg->height; cam.margin = cfg->margin;
+    if (int rc = check_cull_cfg(&cam, depth)) return rc;
+    if (int rc = check_mesh_shape(cfg->nx, cfg->ny, cfg->nz)) return rc;
+    if (n_frames == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::tsdf_integrate(*cfg, tsdf, weight, color, depth, rgbx, reinterpret_cast<const int*>(inst), poses, reinterpret_cast<const int*>(slots),
+                              n_frames, static_cast<hipStream_t>(stream));
 }
 
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {

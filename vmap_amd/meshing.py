@@ -228,10 +228,15 @@ def grid_points(shape, affine, device="cuda:0"):
     return pts
 
 
-def extract_mesh(volume: torch.Tensor, level: float = 0.5, affine=None):
+def extract_mesh(volume: torch.Tensor, level: float = 0.5, affine=None, valid=None, return_edges=False):
     """Marching cubes on the device over a CUDA float32 [nx, ny, nz] volume (any side >= 2).  ``affine``: optional [3,4] (rows
     [A | b]) applied to the index-space vertices, the normals mapped by A^-T.  Returns a ``Mesh`` (no colours), or ``None`` where
-    the reference's vis.marching_cubes returns None: no face (which covers a level outside the volume's range)."""
+    the reference's vis.marching_cubes returns None: no face (which covers a level outside the volume's range).
+
+    ``valid``: optional mask of the volume's shape (non-zero = the point holds a value).  Only cells whose eight corners are all valid
+    exist, a vertex is emitted only on an edge of an existing cell, and the normals treat an invalid neighbour like the grid border
+    (the contract of vmapstep_mesh_count_valid); all ones gives the unmasked mesh bit for bit.  ``return_edges``: return
+    ``(mesh, edge_ids)`` with the int32 [V] tensor owning point * 3 + axis of every vertex (``(None, None)`` without a face)."""
     if not isinstance(volume, torch.Tensor) or not volume.is_cuda or volume.dtype != torch.float32 or volume.dim() != 3:
         raise _lib.VmapStepError("extract_mesh: a CUDA float32 [nx, ny, nz] volume is required (no CPU fallback)")
     lib = _lib.load()
@@ -241,17 +246,26 @@ def extract_mesh(volume: torch.Tensor, level: float = 0.5, affine=None):
     ws, ws_ptr, nbytes = _devmem.workspace(lib, lib.vmapstep_mesh_workspace_bytes, dev, *shape)
     stream = _devmem.stream(dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    _lib.check(lib.vmapstep_mesh_count(vol.data_ptr(), *shape, float(level), counts.data_ptr(), ws_ptr, nbytes, stream), lib)
+    mask = None
+    if valid is not None:
+        mask = torch.as_tensor(valid).to(dev)
+        if tuple(mask.shape) != shape:
+            raise _lib.VmapStepError("extract_mesh: valid must have the volume's shape")
+        mask = (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
+    mask_ptr = None if mask is None else mask.data_ptr()
+    _lib.check(lib.vmapstep_mesh_count_valid(vol.data_ptr(), mask_ptr, *shape, float(level), counts.data_ptr(), ws_ptr, nbytes, stream), lib)
     nv, nf = (int(x) for x in counts.cpu())              # the one host synchronisation
     if nf == 0:
-        return None
+        return (None, None) if return_edges else None
     verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
     normals = torch.empty(nv, 3, dtype=torch.float32, device=dev)
     faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
     aff = None if affine is None else _f12(affine)
-    _lib.check(lib.vmapstep_mesh_emit(vol.data_ptr(), *shape, float(level), aff, verts.data_ptr(), normals.data_ptr(), faces.data_ptr(),
-                                      nv, nf, ws_ptr, nbytes, stream), lib)
-    return Mesh(verts, faces, normals)
+    edges = torch.empty(nv, dtype=torch.int32, device=dev) if return_edges else None
+    _lib.check(lib.vmapstep_mesh_emit_valid(vol.data_ptr(), mask_ptr, *shape, float(level), aff, verts.data_ptr(), normals.data_ptr(),
+                                            faces.data_ptr(), None if edges is None else edges.data_ptr(), nv, nf, ws_ptr, nbytes, stream), lib)
+    mesh = Mesh(verts, faces, normals)
+    return (mesh, edges) if return_edges else mesh
 
 
 def bound_affine(bound, bound_extent, grid_dim, obj_center=None):
