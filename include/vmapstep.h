@@ -1020,6 +1020,70 @@ typedef struct vmapstep_tsdf_cfg {
 int vmapstep_tsdf_integrate(const vmapstep_tsdf_cfg* cfg, float* tsdf, float* weight, float* color, const float* depth, const uint8_t* rgbx,
                             const int32_t* inst, const float* poses, const int32_t* slots, int32_t n_frames, void* stream);
 
+/* ---- TSDF ray cast: depth, status, normal and colour images of a TSDF volume, with no mesh in between ---------------------------------
+ * The contract is this project's own (csrc/raycast_rules.h is the definition); float32 throughout, every fma ONE fused operation, every
+ * other operation rounded on its own, IEEE division and square root, rintf half to even.
+ *
+ * Volume: the tsdf section's tsdf, weight and color, read only.  Views: DEVICE float32 [n_views][12], per view M = A^-1 T_wc (camera ->
+ * voxel index, rows [R | o]) composed on the host in float64 and rounded once; the contract starts from these floats.  A view whose 12
+ * floats are all zero is an unused slot: every pixel is a miss.  normal_map: the float32 rounding of A^-T, 9 floats per volume.
+ *
+ * Per pixel (w, h) of a [width][height] image (width-major):
+ *   u = ((float)w - cx) / fx, v = ((float)h - cy) / fy: the ray is (u, v, 1) z in the camera frame, z = depth along the optical axis;
+ *   o_r = M[4r+3], d_r = fma(M[4r+1], v, fma(M[4r], u, M[4r+2])): the point at z is p_r = fma(d_r, z, o_r), in voxel indices;
+ *   range: z0 = min_depth, z1 = max_depth; per axis with hi = n - 1: d_r == 0 -> a miss unless 0 <= o_r <= hi, no constraint otherwise;
+ *     else ta = (0 - o_r) / d_r, tb = (hi - o_r) / d_r, z0 = fmaxf(z0, fminf(ta, tb)), z1 = fminf(z1, fmaxf(ta, tb)); a miss unless z0 <= z1;
+ *   samples: dz = step / sqrtf(fma(u, u, fma(v, v, 1))) (step is metres along the ray), z_n = fma((float)n, dz, z0), n = 0, 1, ...;
+ *     the ray has left the range at the first n with !(z_n <= z1), and has run out of steps at n == max_steps (checked in that order);
+ *   value: p outside [0, n-1] on an axis (or NaN) is an invalid sample; else the cell i0 = min((int)floorf(p), n - 2), t = p - (float)i0
+ *     per axis, lerps fma(t, b - a, a) along k, then j, then i; valid iff all eight corners have weight >= min_weight;
+ *   march, with one piece of state (the previous sample, if it was valid and > 0): an invalid sample clears the state; a valid f <= 0
+ *     with the state set is a hit at z* = fma(z_n - z_prev, f_prev / (f_prev - f), z_prev); a valid f < 0 without state ends the ray
+ *     behind a surface; a valid f == 0 (or NaN) without state leaves the state cleared and the ray goes on; a valid f > 0 sets the state.
+ * Outputs: depth (z* or 0); status (0 missed the volume or the depth range, 1 hit, 2 left the range without a crossing, 3 ended behind a
+ * surface, 4 ran out of steps); normal (world frame, unit length, towards increasing TSDF = free space): g_a = f(p* + e_a) - f(p* - e_a)
+ * from six samples as above, n_r = fma(N[3r+2], g2, fma(N[3r+1], g1, N[3r] * g0)) with N = normal_map, divided by
+ * sqrtf(fma(n0, n0, fma(n1, n1, n2 * n2))); all zero when one of the six samples is invalid or outside or the length is not > 0;
+ * color_out (r, g, b, 255): over the corners of p*'s cell with colour weight wc > 0, in the order (di, dj, dk), dk fastest, the weight
+ * q = (qi * qj) * qk (q_ = t or 1 - t) accumulates s = s + q and c = fma(q, colour, c); the byte is rintf(c / s) clamped to 0..255; all
+ * zero when no corner has colour or s is not > 0.  Every element of every output is written, exactly once; nothing is accumulated.
+ *
+ * Brick classes: the cells are cut into bricks of 8 x 8 x 8, cell (i, j, k) in brick (i >> 3, j >> 3, k >> 3); one byte per brick,
+ * [bx][by][bz] with b_ = (n_ - 1 + 7) >> 3: 1 = EMPTY (no cell of the brick has eight valid corners: every sample in it is invalid),
+ * 2 = FREE (every voxel of the brick, the apron shared with its neighbours included, is valid and exactly 1.0f: every sample in it is
+ * valid and exactly 1.0, by the lerp form), 0 = MIXED (sampled in full).  vmapstep_tsdf_bricks writes them from tsdf and weight in one
+ * pass; vmapstep_tsdf_bricks_bytes is the table's size padded to 16 bytes, and the table is 16-byte aligned.  The ray cast takes a
+ * sample's result from the class of its cell's brick and gathers nothing in an EMPTY or FREE one: the same bits for every output as
+ * with bricks == NULL or flags & 1 (ignore the classes), whatever the volume holds - provided the table was built from the same tsdf,
+ * weight and min_weight.
+ *
+ * Everything is enqueued on `stream`, nothing waits; n_views == 0 is VMAPSTEP_OK and writes nothing.  Before anything is enqueued:
+ * VMAPSTEP_ERR_ARGUMENT for a null cfg, tsdf, weight, views, depth or status (bricks: a null tsdf, weight or bricks); a pointer that is
+ * not aligned to its element (color and bricks: 16 bytes; color_out: 4); color_out without color; step, min_weight, fx or fy not finite
+ * or not > 0; cx or cy not finite; min_depth not finite or < 0; max_depth not > min_depth; max_steps outside 1 .. 2^24 - 1; width or
+ * height < 1 or width * height >= 2^31 / 12; a normal_map that is not finite; n_views < 0 or n_views * width * height >= 2^40.
+ * VMAPSTEP_ERR_UNSUPPORTED for a volume outside the mesh section's limits (each side 2..1024, 3*nx*ny*nz < 2^31). */
+#define VMAPSTEP_RAYCAST_IGNORE_BRICKS 1
+typedef struct vmapstep_raycast_cfg {
+    int32_t nx, ny, nz;
+    int32_t width, height;
+    int32_t max_steps;             /* 1 .. 2^24 - 1 samples per ray */
+    int32_t flags;                 /* VMAPSTEP_RAYCAST_IGNORE_BRICKS: the class table is not read (the A/B and equality switch) */
+    int32_t reserved;              /* 0 */
+    float fx, fy, cx, cy;
+    float min_depth, max_depth;    /* the ray is cast over min_depth <= z <= max_depth */
+    float step;                    /* metres along the ray, > 0 */
+    float min_weight;              /* a voxel is valid iff weight >= min_weight; > 0 */
+    float normal_map[9];           /* float32 rounding of A^-T, rows */
+    float reserved_f;              /* 0 */
+} vmapstep_raycast_cfg;
+
+int vmapstep_tsdf_bricks_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes);
+int vmapstep_tsdf_bricks(int32_t nx, int32_t ny, int32_t nz, float min_weight, const float* tsdf, const float* weight, uint8_t* bricks,
+                         void* stream);
+int vmapstep_tsdf_raycast(const vmapstep_raycast_cfg* cfg, const float* tsdf, const float* weight, const float* color, const uint8_t* bricks,
+                          const float* views, int32_t n_views, float* depth, uint8_t* status, float* normal, uint8_t* color_out, void* stream);
+
 /* Measurement hook: vmapstep_train_steps with every launch of the dominant kernel timed in the real step sequence (prep,
  * then main / finalize alternating); waits for the device and returns average durations in milliseconds:
  * main_kernel_ms[0] = the dispatch's own begin -> end timestamps (events attached to the launch with hipExtLaunchKernel:

@@ -6,4 +6,13 @@ does, and raises if it is missing - there is no CPU or eager-PyTorch fallback fo
 """
 from . import layout  # noqa: F401
 
-__all__ = ["layout", "synth", "fields", "trainer", "ensemble", "step", "visibility", "components", "raster", "odometry", "tsdf"]
+__all__ = ["layout", "synth", "fields", "trainer", "ensemble", "step", "visibility", "components", "raster", "odometry", "tsdf",
+           "TSDFVolume", "VolumeView"]
+
+
+def __getattr__(name):
+    """``vmap_amd.TSDFVolume`` / ``vmap_amd.VolumeView``: resolved on first use, so that importing the package stays light."""
+    if name in ("TSDFVolume", "VolumeView"):
+        from . import tsdf
+        return getattr(tsdf, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

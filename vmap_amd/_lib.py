@@ -194,6 +194,19 @@ class TsdfCfg(ctypes.Structure):
                 ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("trunc", ctypes.c_float), ("max_weight", ctypes.c_float)]
 
 
+class RaycastCfg(ctypes.Structure):
+    """vmapstep_raycast_cfg: the volume's shape, the image size, the camera, the depth range and the rules of vmapstep_tsdf_raycast."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("max_steps", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_depth", ctypes.c_float), ("max_depth", ctypes.c_float), ("step", ctypes.c_float), ("min_weight", ctypes.c_float),
+                ("normal_map", ctypes.c_float * 9), ("reserved_f", ctypes.c_float)]
+
+
+RAYCAST_IGNORE_BRICKS = 1
+RAYCAST_MISS, RAYCAST_HIT, RAYCAST_LEFT, RAYCAST_BEHIND, RAYCAST_STEPS = 0, 1, 2, 3, 4
+RAYCAST_MAX_STEPS = (1 << 24) - 1
+
 ICP_MAX_LEVELS = 4
 ICP_MAX_ITERATIONS = 64
 ICP_MAX_PIXELS = 1 << 20                   # the bound under which the int64 sums cannot overflow (csrc/icp_rules.h)
@@ -224,6 +237,7 @@ EXPORTS = (
     "vmapstep_raster_workspace_bytes", "vmapstep_raster_count", "vmapstep_raster_draw", "vmapstep_raster_resolve", "vmapstep_depth_compare",
     "vmapstep_icp_maps_bytes", "vmapstep_icp_pyramid", "vmapstep_icp_sums", "vmapstep_icp_track",
     "vmapstep_mesh_count_valid", "vmapstep_mesh_emit_valid", "vmapstep_tsdf_integrate",
+    "vmapstep_tsdf_bricks_bytes", "vmapstep_tsdf_bricks", "vmapstep_tsdf_raycast",
 )
 
 _libs = {}
@@ -405,7 +419,11 @@ def load(path=None):
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.vmapstep_tsdf_integrate.argtypes = [ctypes.POINTER(TsdfCfg)] + [ctypes.c_void_p] * 8 + [ctypes.c_int32, ctypes.c_void_p]
-    for fn in ("vmapstep_mesh_count_valid", "vmapstep_mesh_emit_valid", "vmapstep_tsdf_integrate"):
+    lib.vmapstep_tsdf_bricks_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.vmapstep_tsdf_bricks.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float] + [ctypes.c_void_p] * 4
+    lib.vmapstep_tsdf_raycast.argtypes = [ctypes.POINTER(RaycastCfg)] + [ctypes.c_void_p] * 5 + [ctypes.c_int32] + [ctypes.c_void_p] * 5
+    for fn in ("vmapstep_mesh_count_valid", "vmapstep_mesh_emit_valid", "vmapstep_tsdf_integrate", "vmapstep_tsdf_bricks_bytes",
+               "vmapstep_tsdf_bricks", "vmapstep_tsdf_raycast"):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("vmapstep_filter_workspace_bytes", "vmapstep_filter_stats", "vmapstep_filter_emit", "vmapstep_filter_write",
                "vmapstep_voxel_points", "vmapstep_cull_mark", "vmapstep_cull_workspace_bytes", "vmapstep_cull_faces_count",

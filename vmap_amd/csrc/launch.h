@@ -1,5 +1,5 @@
 // launch.h - host-side launchers of the kernel families, one translation unit per family so that hipcc compiles them side
-// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip, k_icp.hip, k_tsdf.hip; no device code crosses
+// by side (build(): vmapstep.hip = the C ABI, k_f32.hip, k_s32.hip, k_ws.hip, k_ws8.hip, k_wp.hip, k_misc.hip, k_mesh.hip, k_eval.hip, k_bounds.hip, k_view.hip, k_ingest.hip, k_filter.hip, k_track.hip, k_cull.hip, k_components.hip, k_raster.hip, k_icp.hip, k_tsdf.hip, k_raycast.hip; no device code crosses
 // a unit, so no relocatable device code is needed).  Every function only ENQUEUES on `st` and returns a vmapstep status.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@ struct vmapstep_cull_cfg;
 struct vmapstep_raster_cfg;
 struct vmapstep_icp_cfg;
 struct vmapstep_tsdf_cfg;
+struct vmapstep_raycast_cfg;
 
 namespace vl {
 
@@ -188,5 +189,11 @@ int icp_track(const vmapstep_icp_cfg& cfg, const void* src_maps, const void* mod
 // checked that what cfg makes the kernel read is there)
 int tsdf_integrate(const vmapstep_tsdf_cfg& cfg, float* tsdf, float* weight, float* color, const float* depth, const unsigned char* rgbx,
                    const int* inst, const float* t_wc, const int* slots, int n_frames, hipStream_t st);
+
+// k_raycast.hip: the TSDF ray cast (raycast_kernels.h).  tsdf_bricks = one launch, a workgroup per (a, b) column of bricks;
+// tsdf_raycast = one launch per 65535 views; bricks null = the classes are not read; color / normal / color_out may be null
+int tsdf_bricks(int nx, int ny, int nz, float min_weight, const float* tsdf, const float* weight, unsigned char* bricks, hipStream_t st);
+int tsdf_raycast(const vmapstep_raycast_cfg& cfg, const float* tsdf, const float* weight, const float* color, const unsigned char* bricks, int n_bricks,
+                 const float* views, int n_views, float* depth, unsigned char* status, float* normal, unsigned char* color_out, hipStream_t st);
 
 }  // namespace vl

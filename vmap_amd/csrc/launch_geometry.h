@@ -133,6 +133,19 @@ constexpr int kTsdfTile = kTsdfWG * kVoxelsPer;   // voxels per workgroup
 constexpr int kTsdfChunk = 32;             // frames whose poses and image offsets a workgroup stages in LDS at a time
 }  // namespace vtsdf
 
+namespace vray {                           // the TSDF ray cast (raycast_kernels.h)
+constexpr int kBricksWG = 256;             // tsdf_bricks: one workgroup per (a, b) column of bricks, a lane per k; four waves
+constexpr int kRaycastWG = 256;            // tsdf_raycast: four waves, each an 8 x 8 pixel tile (h fast)
+constexpr int kTile = 8;
+constexpr int kTilesPerWG = kRaycastWG / 64;
+constexpr int kMaxViewsPerLaunch = 65535;  // views ride on grid.y; more views = more launches (a pixel's result does not depend on it)
+#ifdef VMAPSTEP_AB
+constexpr int kClassLdsBudget = 16;        // the measurement build: every test volume's class table misses it and is read from global memory
+#else
+constexpr int kClassLdsBudget = 32768;     // bytes of class table a workgroup stages in LDS: a 256^3 volume's 32^3 bricks just fit
+#endif
+}  // namespace vray
+
 // ---- workspace layouts and launch plans (namespace vl: what launch.h's launchers and the C ABI build on) ----
 namespace vl {
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "raycast_rules.h"       // brick_dim and the step limit only
 // layouts only (image sizes, LDS / scratch budgets of the plan): no kernel of the headers it includes is instantiated in this unit
 #include "step_plan.h"
 
@@ -1493,6 +1494,57 @@ int vmapstep_tsdf_integrate(const vmapstep_tsdf_cfg* cfg, float* tsdf, float* we
     VMAPSTEP_ON_STREAM_DEVICE(stream);
     return vl::tsdf_integrate(*cfg, tsdf, weight, color, depth, rgbx, reinterpret_cast<const int*>(inst), poses, reinterpret_cast<const int*>(slots),
                               n_frames, static_cast<hipStream_t>(stream));
+}
+
+// ---- TSDF ray cast -----------------------------------------------------------------------------------------------------------------
+static size_t bricks_count(int32_t nx, int32_t ny, int32_t nz) {
+    return (size_t)rc::brick_dim(nx) * rc::brick_dim(ny) * rc::brick_dim(nz);
+}
+
+int vmapstep_tsdf_bricks_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes) {
+    if (!bytes) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: bytes is null");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    *bytes = (bricks_count(nx, ny, nz) + 15) / 16 * 16;
+    return VMAPSTEP_OK;
+}
+
+int vmapstep_tsdf_bricks(int32_t nx, int32_t ny, int32_t nz, float min_weight, const float* tsdf, const float* weight, uint8_t* bricks,
+                         void* stream) {
+    if (!tsdf || !weight || !bricks) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: tsdf, weight or bricks is null");
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((at(tsdf) | at(weight)) % 4 || at(bricks) % 16)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: a pointer is not aligned to its element (bricks: 16 bytes)");
+    if (!(min_weight > 0.0f) || !std::isfinite(min_weight)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: min_weight must be finite and > 0");
+    if (int rc = check_mesh_shape(nx, ny, nz)) return rc;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::tsdf_bricks(nx, ny, nz, min_weight, tsdf, weight, bricks, static_cast<hipStream_t>(stream));
+}
+
+int vmapstep_tsdf_raycast(const vmapstep_raycast_cfg* cfg, const float* tsdf, const float* weight, const float* color, const uint8_t* bricks,
+                          const float* views, int32_t n_views, float* depth, uint8_t* status, float* normal, uint8_t* color_out, void* stream) {
+    if (!cfg) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: cfg is null");
+    if (!tsdf || !weight || !views || !depth || !status) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: tsdf, weight, views, depth or status is null");
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if ((at(tsdf) | at(weight) | at(views) | at(depth) | at(normal) | at(color_out)) % 4 || (at(color) | at(bricks)) % 16)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: a pointer is not aligned to its element (color, bricks: 16 bytes; color_out: 4)");
+    if (color_out && !color) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: color_out needs a colour volume");
+    if (!(cfg->step > 0.0f) || !std::isfinite(cfg->step)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: step must be finite and > 0");
+    if (!(cfg->min_weight > 0.0f) || !std::isfinite(cfg->min_weight)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: min_weight must be finite and > 0");
+    if (!(cfg->fx > 0.0f) || !(cfg->fy > 0.0f) || !std::isfinite(cfg->fx) || !std::isfinite(cfg->fy) || !std::isfinite(cfg->cx) || !std::isfinite(cfg->cy))
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: the camera must be finite with fx, fy > 0");
+    if (!(cfg->min_depth >= 0.0f) || !std::isfinite(cfg->min_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: min_depth must be finite and >= 0");
+    if (!(cfg->max_depth > cfg->min_depth)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: max_depth must be > min_depth");
+    if (cfg->max_steps < 1 || cfg->max_steps >= rc::kMaxStepsLimit) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: max_steps=%d outside 1 .. 2^24 - 1", cfg->max_steps);
+    if (cfg->width < 1 || cfg->height < 1 || (long long)cfg->width * cfg->height >= (1ll << 31) / 12)
+        return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: width=%d height=%d", cfg->width, cfg->height);
+    for (int e = 0; e < 9; ++e)
+        if (!std::isfinite(cfg->normal_map[e])) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: normal_map is not finite");
+    if (n_views < 0 || (long long)n_views * cfg->width * cfg->height >= (1ll << 40)) return fail(VMAPSTEP_ERR_ARGUMENT, "raycast: n_views=%d", n_views);
+    if (int rc = check_mesh_shape(cfg->nx, cfg->ny, cfg->nz)) return rc;
+    if (n_views == 0) return VMAPSTEP_OK;
+    VMAPSTEP_ON_STREAM_DEVICE(stream);
+    return vl::tsdf_raycast(*cfg, tsdf, weight, color, (cfg->flags & VMAPSTEP_RAYCAST_IGNORE_BRICKS) ? nullptr : bricks, (int)bricks_count(cfg->nx, cfg->ny, cfg->nz),
+                            views, n_views, depth, status, normal, color_out, static_cast<hipStream_t>(stream));
 }
 
 int vmapstep_sample_workspace_bytes(int32_t n_obj, size_t* bytes) {

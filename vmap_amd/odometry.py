@@ -294,6 +294,21 @@ class DepthTracker:
         self.set_model(r.depth[0], self.t_wc.astype(np.float32).astype(np.float64))
         return self.track(depth)
 
+    def track_to_volume(self, volume, depth, **raycast_kw):
+        """Ray-casts a ``tsdf.TSDFVolume`` at the last pose (``TSDFVolume.raycast``; ``raycast_kw`` goes to it, ``min_depth`` and
+        ``max_depth`` default to the tracker's own), makes that the model, then tracks ``depth`` against it."""
+        if self.t_wc is None:
+            raise _lib.VmapStepError("DepthTracker.track_to_volume: no pose yet (set_model, or set t_wc)")
+        dev = _device()
+        self._check(depth, dev)
+        raycast_kw.setdefault("min_depth", float(self.params["min_depth"]))
+        raycast_kw.setdefault("max_depth", float(self.params["max_depth"]))
+        raycast_kw.setdefault("normals", False)
+        view = volume.raycast(self.t_wc, self.intrinsics, self.width, self.height, **raycast_kw)
+        # the volume was cast from the float32 rounding of the pose: that rounding is the model's pose
+        self.set_model(view.depth[0], view.t_wc[0].astype(np.float64))
+        return self.track(depth)
+
     def track_to_view(self, view, depth, min_opacity, t_wc=None):
         """Tracks ``depth`` against a ``render.View``'s depth image, zeroed where its opacity is below ``min_opacity``; ``t_wc``: the
         pose the view was rendered from (default: the last pose)."""

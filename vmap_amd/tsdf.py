@@ -9,10 +9,15 @@ inside; a voxel no frame has updated has weight 0 and yields no surface.  Frames
 once per ``integrate`` call, whatever the number of frames, and the result depends on the order of the frames alone - one call over K
 frames equals two calls over its halves bit for bit.
 
-    python -m vmap_amd.tsdf FRAMES.npz OUT.ply --voxel-size X --trunc Y [--obj-id N]
+``TSDFVolume.raycast`` reads a volume out directly as depth, status, normal and colour images from any poses, with no mesh in between
+(csrc/raycast_rules.h, csrc/raycast_kernels.h, the raycast section of include/vmapstep.h): the model image of
+``DepthTracker.track_to_volume``, and a volume-side input of ``raster.compare_depth``.
+
+    python -m vmap_amd.tsdf FRAMES.npz OUT.ply --voxel-size X --trunc Y [--obj-id N] [--views OUT.npz]
 
 reads depth [K,W,H], t_wc [K,4,4], intrinsics [4] (the file ``python -m vmap_amd.evaluation --frames`` reads) and optionally rgb
-[K,W,H,3] uint8 and inst [K,W,H] integers."""
+[K,W,H,3] uint8 and inst [K,W,H] integers.  ``--views`` also writes the ray cast of the fused volume at the frames' own poses: depth,
+status, normal, t_wc and, with rgb, color."""
 from __future__ import annotations
 
 import ctypes
@@ -25,9 +30,20 @@ from .bounds import _intrinsics4
 from .meshing import BoundingBox, bound_affine, extract_mesh
 from .visibility import _device, _slots
 
-__all__ = ["TSDFVolume", "fuse_object"]
+__all__ = ["TSDFVolume", "VolumeView", "fuse_object"]
 
 FLT_MAX = float(np.finfo(np.float32).max)      # the default max_depth: every finite depth counts, inf does not
+
+
+class VolumeView:
+    """What ``TSDFVolume.raycast`` returns, on the volume's device: ``depth`` float32 [K, W, H] (0 = no hit), ``status`` uint8 [K, W, H]
+    (``MISS`` the volume or the depth range, ``HIT``, ``LEFT`` the range without a crossing, ended ``BEHIND`` a surface, ran out of
+    ``STEPS``), ``normal`` float32 [K, W, H, 3] or None (world frame, unit length, to free space; zero where refused), ``color`` uint8
+    [K, W, H, 4] or None, and ``t_wc`` float32 [K, 4, 4] on the host: the float32 poses the images were actually cast from."""
+    MISS, HIT, LEFT, BEHIND, STEPS = _lib.RAYCAST_MISS, _lib.RAYCAST_HIT, _lib.RAYCAST_LEFT, _lib.RAYCAST_BEHIND, _lib.RAYCAST_STEPS
+
+    def __init__(self, depth, status, normal, color, t_wc):
+        self.depth, self.status, self.normal, self.color, self.t_wc = depth, status, normal, color, t_wc
 
 
 class TSDFVolume:
@@ -123,6 +139,73 @@ class TSDFVolume:
         return self.integrate(store.depth, store.t_wc, intrinsics, rgb=store.rgbx if self.color is not None else None,
                               inst=store.inst if obj_id is not None else None, obj_id=obj_id, slots=slots, **kw)
 
+    def raycast(self, t_wc, intrinsics, width, height, *, min_depth, max_depth, min_weight=1.0, step=None, max_steps=4096, normals=True,
+                color=None, use_bricks=True, library=None):
+        """Depth, status, normal and colour images of the volume from the poses ``t_wc`` [K, 4, 4] (camera to world; a single [4, 4] is
+        K = 1; an all-zero pose is an unused slot whose pixels all miss) -> ``VolumeView``.  A ray is cast over ``min_depth`` <= z <=
+        ``max_depth`` in samples ``step`` metres apart along the ray (default ``trunc / 2``), at most ``max_steps`` of them, and hits where
+        the TSDF, trilinear over voxels of weight >= ``min_weight``, first goes from > 0 to <= 0.  ``color``: default, whether the volume
+        has colour.  The brick classes (exact empty-space skipping) are rebuilt on every call - one read of the volume, amortised over
+        the K views; nothing is cached, ``tsdf`` and ``weight`` being public tensors.  ``use_bricks=False`` marches without them and
+        gives the same bits.  ``library``: another build of the library (the measurement build of tests/tools)."""
+        lib = _lib.load(library)
+        dev = self.device
+        poses = np.asarray(t_wc.detach().cpu().numpy() if isinstance(t_wc, torch.Tensor) else t_wc, np.float64)
+        if poses.shape == (4, 4):
+            poses = poses[None]
+        if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+            raise _lib.VmapStepError("raycast: t_wc [K, 4, 4]")
+        color = self.color is not None if color is None else bool(color)
+        if color and self.color is None:
+            raise _lib.VmapStepError("raycast: color=True needs a colour volume")
+        step = self.trunc / 2 if step is None else float(step)
+        width, height, K = int(width), int(height), len(poses)
+        # the float32 rounding of the poses is what the images are cast from; M = A^-1 T_wc in float64, rounded once
+        t32 = poses.astype(np.float32)
+        A4 = np.eye(4)
+        A4[:3] = self.affine
+        A_inv = np.linalg.inv(A4)
+        M = np.zeros((K, 12), np.float64)
+        for k in range(K):
+            if t32[k, :3].any():
+                M[k] = (A_inv @ t32[k].astype(np.float64))[:3].reshape(12)
+        nmap = (ctypes.c_float * 9)(*np.linalg.inv(self.affine[:, :3]).T.astype(np.float32).reshape(-1).tolist())
+        fx, fy, cx, cy = _intrinsics4(intrinsics)
+        cfg = _lib.RaycastCfg(*self.shape, width, height, int(max_steps), 0 if use_bricks else _lib.RAYCAST_IGNORE_BRICKS, 0, fx, fy, cx, cy,
+                              float(min_depth), float(max_depth), step, float(min_weight), nmap, 0.0)
+        with torch.cuda.device(dev):
+            views = torch.from_numpy(M.astype(np.float32)).to(dev)
+            depth = torch.empty((K, width, height), dtype=torch.float32, device=dev)
+            status = torch.empty((K, width, height), dtype=torch.uint8, device=dev)
+            normal = torch.empty((K, width, height, 3), dtype=torch.float32, device=dev) if normals else None
+            col = torch.empty((K, width, height, 4), dtype=torch.uint8, device=dev) if color else None
+            stream = _devmem.stream(dev)
+            bricks = None
+            if use_bricks and K:
+                nb = ctypes.c_size_t()
+                _lib.check(lib.vmapstep_tsdf_bricks_bytes(*self.shape, ctypes.byref(nb)), lib)
+                bricks = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+                _lib.check(lib.vmapstep_tsdf_bricks(*self.shape, float(min_weight), self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                                    bricks.data_ptr(), stream), lib)
+            _lib.check(lib.vmapstep_tsdf_raycast(ctypes.byref(cfg), self.tsdf.data_ptr(), self.weight.data_ptr(),
+                                                 None if self.color is None else self.color.data_ptr(),
+                                                 None if bricks is None else bricks.data_ptr(), views.data_ptr(), K, depth.data_ptr(),
+                                                 status.data_ptr(), None if normal is None else normal.data_ptr(),
+                                                 None if col is None else col.data_ptr(), stream), lib)
+        return VolumeView(depth, status, normal, col, t32)
+
+    def brick_classes(self, min_weight=1.0, library=None):
+        """uint8 [bx, by, bz]: the class of every brick of 8 x 8 x 8 cells (0 mixed, 1 empty, 2 free) as ``raycast`` builds them."""
+        lib = _lib.load(library)
+        nb = ctypes.c_size_t()
+        _lib.check(lib.vmapstep_tsdf_bricks_bytes(*self.shape, ctypes.byref(nb)), lib)
+        with torch.cuda.device(self.device):
+            bricks = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.vmapstep_tsdf_bricks(*self.shape, float(min_weight), self.tsdf.data_ptr(), self.weight.data_ptr(), bricks.data_ptr(),
+                                                _devmem.stream(self.device)), lib)
+        bd = tuple((s + 6) >> 3 for s in self.shape)
+        return bricks[:bd[0] * bd[1] * bd[2]].reshape(bd)
+
     def extract_mesh(self, min_weight=1.0, min_component_area=None, largest_components=None):
         """The surface as a ``Mesh`` in world coordinates, or ``None``: marching cubes at TSDF = 0 over the voxels whose weight is at
         least ``min_weight``.  The kernels call a corner 'above' where the value is greater than the level and point normals to
@@ -176,6 +259,7 @@ def main(argv=None):
     ap.add_argument("--min-weight", type=float, default=1.0)
     ap.add_argument("--min-component-area", type=float, default=None, metavar="X")
     ap.add_argument("--largest-components", type=int, default=None, metavar="K")
+    ap.add_argument("--views", default=None, metavar="OUT.npz", help="also write the ray cast of the volume at the frames' own poses")
     args = ap.parse_args(argv)
     with np.load(args.frames) as fr:
         depth, t_wc, intrinsics = fr["depth"], fr["t_wc"], fr["intrinsics"]
@@ -189,6 +273,15 @@ def main(argv=None):
     box = _box_of_frames(depth, t_wc, intrinsics, inst, args.obj_id, args.max_depth)
     vol = TSDFVolume.from_bound(box, voxel_size=args.voxel_size, trunc=args.trunc, color=rgb is not None, device=dev)
     vol.integrate(d, t_wc, intrinsics, rgb=rgb, inst=ins, obj_id=args.obj_id, max_depth=args.max_depth)
+    if args.views is not None:
+        usable = d[torch.isfinite(d) & (d > 0) & (d <= args.max_depth)]
+        far = float(usable.max()) if usable.numel() else 1.0
+        view = vol.raycast(t_wc, intrinsics, d.shape[1], d.shape[2], min_depth=0.0, max_depth=far + 2 * args.trunc, min_weight=args.min_weight)
+        arrays = dict(depth=view.depth.cpu().numpy(), status=view.status.cpu().numpy(), normal=view.normal.cpu().numpy(), t_wc=view.t_wc)
+        if view.color is not None:
+            arrays["color"] = view.color.cpu().numpy()
+        np.savez(args.views, **arrays)
+        print(f"{args.views}: {len(view.t_wc)} views, {int((view.status == VolumeView.HIT).sum())} pixels hit")
     mesh = vol.extract_mesh(args.min_weight, args.min_component_area, args.largest_components)
     if mesh is None:
         print("no surface")
