@@ -79,6 +79,8 @@ typedef struct vmapstep_tuning {
                                    /* bit 5 = the former order of its front: all encoding planes split and the        */
                                    /* backward's cos * pi * 2^f formed in front of the image barrier, none under the   */
                                    /* forward's matrix chains (A/B: same bits)                                         */
+                                   /* bit 6 = its former backward: the mid1 / mid2 chunks and d(projection) products   */
+                                   /* untied, the bias sums as read-modify-writes (A/B: same bits)                     */
 } vmapstep_tuning;
 
 typedef struct vmapstep_shape {

@@ -23,11 +23,33 @@ int main_of(const vk::StepArgs& a, hipStream_t st) {
     VL_LAUNCH_MAIN(kern, dim3(grid), dim3(vk::kWG), vk::Img32s::LDS_BYTES, st, a);
     return launched("step_main_s32");
 }
+template <bool MULTI, bool STAMPS, bool W3, bool B6>
+int main_ob(const vk::StepArgs& a, hipStream_t st) {
+    auto kern = vk::step_main_s32_ob<MULTI, STAMPS, W3, B6>;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), vk::Img32s::LDS_BYTES, "step_main_s32")) return rc;
+    const int grid = a.xcd_affine ? 8 * ((a.n_obj + 7) / 8) * a.NW : a.n_obj * a.NW;
+    VL_LAUNCH_MAIN(kern, dim3(grid), dim3(vk::kWG), vk::Img32s::LDS_BYTES, st, a);
+    return launched("step_main_s32");
+}
 #endif
 template <bool BWD, bool STAMPS>
 int main_bs(const vk::StepArgs& a, hipStream_t st) {
     const bool multi = a.NW < a.NG;
 #ifdef VMAPSTEP_AB
+    if (a.ab_flags & 8) {                    // tuning.ws_flags bit 6: the former backward (training instantiations; phase stamps: float32 weights, three products, one pass)
+        if constexpr (BWD) {
+            if (!(a.ab_flags & 7)) {
+                if constexpr (STAMPS) {
+                    if (!a.weights_bf16 && !a.bwd6 && !multi) return main_ob<false, true, true, false>(a, st);
+                } else {
+                    if (a.weights_bf16) return multi ? main_ob<true, false, false, false>(a, st) : main_ob<false, false, false, false>(a, st);
+                    if (a.bwd6) return multi ? main_ob<true, false, true, true>(a, st) : main_ob<false, false, true, true>(a, st);
+                    return multi ? main_ob<true, false, true, false>(a, st) : main_ob<false, false, true, false>(a, st);
+                }
+            }
+        }
+        return fail(-2, "tuning.ws_flags bit 6 (the former backward of step_main_s32): training steps without bit 3, 4 or 5; phase stamps with float32 weights, the three-product backward and one pass per workgroup only");
+    }
     if (a.ab_flags & 4) {                    // tuning.ws_flags bit 5: the former order of the front (training instantiations)
         if constexpr (BWD && !STAMPS) {
             if (!(a.ab_flags & 3)) {

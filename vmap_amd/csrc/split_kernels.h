@@ -38,6 +38,9 @@
 #ifndef VS_FRONT_PARTS           /* measurement builds only (tests/tools/build_variant.py): what step_main_s32 moves from the front of the image barrier under   */
 #define VS_FRONT_PARTS 15        /* the forward's matrix chains, part by part - bit 0 = the planes of e1[24..47], bit 1 = those of e2, bit 2 = cos * pi * 2^f;   */
 #endif                           /* bit 3 = gap_fill's chunks tied where the source forms them                                                                   */
+#ifndef VS_BACK_PARTS            /* measurement builds only: the parts of the backward's filled stretches - bit 0 = the mask / split chunks of mid1 / mid2 tied    */
+#define VS_BACK_PARTS 7          /* where the source forms them, bit 1 = the d(projection) products tied, bit 2 = the bias sums, head gradients and B_layer sums  */
+#endif                           /* written into their cleared cells without the read (one pass per workgroup)                                                    */
 
 // Measurement builds only (tests/tools/build_variant.py ... -DVS_ABL=<mask>; results WRONG on purpose - the product never defines it):
 // bit 7: step_finalize_s32 does not rewrite the parameter image; bit 4: only the partial-gradient global stores are skipped; bit 5: the finishing (staged reads, sums, stores) is skipped, the staging writes stay;
@@ -688,18 +691,41 @@ __device__ __forceinline__ void mm_dw_il(f32x16& acc, f32x16& accb, const unsign
     }
 }
 // ReLU mask + two-plane split of register pair j of a d-prop result (the VALU work of a hidden unit, one chunk per pair)
-template <int NPD = 2>
+// TIED: the planes are tied where they are formed (after_u(): no instruction).  Untied, a branch between the chain and the planes' first
+// use (the bias sums of mid1 / mid2) makes the compiler sink all eight chunks behind the chain, into the block of that use.
+template <int NPD = 2, bool TIED = false>
 __device__ __forceinline__ void mask_split_pair(int j, const f32x16& v, const unsigned (&hh)[8], unsigned (&dh)[8], unsigned (&dm)[8], unsigned (&dl)[8], float dep) {
     const unsigned u = wv::opaque_u(hh[j]);
     const float va = wv::after(v[2 * j], dep);           // (the tie sits outside the select: inside it the select becomes a branch)
     const float a = (u & 0xFFFFu) != 0u ? va : 0.0f;
     const float b = u > 0xFFFFu ? v[2 * j + 1] : 0.0f;
     const unsigned ph = wv::pack_bf16(a, b);
-    dh[j] = ph;
+    dh[j] = TIED ? wv::after_u(ph, ph) : ph;
     const float ra = a - bf_lo(ph), rb = b - bf_hi(ph);
     const unsigned pm = wv::pack_bf16(ra, rb);
-    dm[j] = pm;
-    if (NPD == 3) dl[j] = wv::pack_bf16(ra - bf_lo(pm), rb - bf_hi(pm));
+    dm[j] = TIED ? wv::after_u(pm, pm) : pm;
+    if (NPD == 3) {
+        const unsigned pl = wv::pack_bf16(ra - bf_lo(pm), rb - bf_hi(pm));
+        dl[j] = TIED ? wv::after_u(pl, pl) : pl;
+    }
+}
+// the ones-column bias sums of mid1 / mid2 (every column of accb holds them: lanes 0 and 32 own the wave's 16 + 16 rows) into the
+// wave's private cells.  ZERO (one pass per workgroup: the cells were cleared at kernel entry and are written once): the same
+// addition 0.0f + x the read-modify-write performs on the cleared cell, as four 16-byte stores without the dependent LDS reads.
+template <bool ZERO>
+__device__ __forceinline__ void bias_sums_put(float* gb, const f32x16& accb, int p31, int hi) {
+    if (p31 == 0) {
+        if constexpr (ZERO) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                static_assert(phi(4, 0) == 8 && phi(3, 1) == 7, "rows 4 q .. 4 q + 3 of a half are consecutive cells");
+                *reinterpret_cast<wv::f32x4*>(gb + phi(4 * q, hi)) = wv::f32x4{0.0f + accb[4 * q], 0.0f + accb[4 * q + 1], 0.0f + accb[4 * q + 2], 0.0f + accb[4 * q + 3]};
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) gb[phi(r, hi)] += accb[r];
+        }
+    }
 }
 // finishing a staged block in two chunks: 0 = the four 16-byte reads of this wave's quarter, 1 = sum + store (or keep, MULTI)
 struct FinState { wv::f32x4 t0, t1, t2, t3; };
@@ -886,11 +912,16 @@ __device__ __forceinline__ void stage_get_s(float (&q)[4], const float* stage, i
 // OF (measurement build only, tuning.ws_flags bit 5): the former order of the front, word for word - all 36 register pairs of the
 // encoding split into planes and the backward's cos * pi * 2^f factors formed in front of the image barrier, the in_layer / mid1 /
 // cat / mid2 chains bare (step_main_s32_of below)
-template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false, bool OF = false>
+// OB (measurement build only, tuning.ws_flags bit 6): the former backward, word for word - the mask / split chunks of mid1 / mid2 and
+// the d(projection) products untied (the compiler places them at their use: behind the chain, and in the B_layer unit), the bias
+// sums, the head gradients and the B_layer sums as read-modify-writes (step_main_s32_ob below)
+template <bool BWD, bool MULTI, bool STAMPS, bool W3, bool B6 = false, bool PV = false, bool OL = false, bool OF = false, bool OB = false>
 __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     static_assert(!B6 || (W3 && BWD), "six-product backward: float32 weights, training instantiations");
     constexpr int OLD = OL ? 7 : VS_LOADS_OLD;     // bit 0: B_layer, bit 1: switches / normalisers, bit 2: z
     constexpr int FP = OF ? 0 : VS_FRONT_PARTS;    // bit 0: e1[24..47], bit 1: e2, bit 2: cfac - under the forward's chains; bit 3: gap_fill tied
+    constexpr int BP = OB ? 0 : VS_BACK_PARTS;     // bit 0: mid1 / mid2 chunks tied, bit 1: d(projection) products tied, bit 2: zero-cell writes (one pass per workgroup)
+    constexpr bool TC = (BP & 1) != 0, TD = (BP & 2) != 0, ZC = (BP & 4) != 0 && !MULTI;
     using I = Img32s;
     using F = Flat32;
     constexpr int H = 32;
@@ -1229,15 +1260,28 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
         ga += wv::swap_half(ga); g0 += wv::swap_half(g0); g1 += wv::swap_half(g1); g2 += wv::swap_half(g2);
         sa += wv::swap_half(sa); s0 += wv::swap_half(s0); s1 += wv::swap_half(s1); s2 += wv::swap_half(s2);
         if (hi == 0) {
-            Gv[I::W_A + p31] += ga;
-            Gv[I::W_OC + p31] += g0;
-            Gv[I::W_OC + H + p31] += g1;
-            Gv[I::W_OC + 2 * H + p31] += g2;
-            if (p31 == 0) {
-                Gv[I::B_A] += sa;
-                Gv[I::B_OC + 0] += s0;
-                Gv[I::B_OC + 1] += s1;
-                Gv[I::B_OC + 2] += s2;
+            if constexpr (ZC) {                     // cleared at kernel entry, written once: the same addition, without the dependent reads
+                Gv[I::W_A + p31] = 0.0f + ga;
+                Gv[I::W_OC + p31] = 0.0f + g0;
+                Gv[I::W_OC + H + p31] = 0.0f + g1;
+                Gv[I::W_OC + 2 * H + p31] = 0.0f + g2;
+                if (p31 == 0) {
+                    Gv[I::B_A] = 0.0f + sa;
+                    Gv[I::B_OC + 0] = 0.0f + s0;
+                    Gv[I::B_OC + 1] = 0.0f + s1;
+                    Gv[I::B_OC + 2] = 0.0f + s2;
+                }
+            } else {
+                Gv[I::W_A + p31] += ga;
+                Gv[I::W_OC + p31] += g0;
+                Gv[I::W_OC + H + p31] += g1;
+                Gv[I::W_OC + 2 * H + p31] += g2;
+                if (p31 == 0) {
+                    Gv[I::B_A] += sa;
+                    Gv[I::B_OC + 0] += s0;
+                    Gv[I::B_OC + 1] += s1;
+                    Gv[I::B_OC + 2] += s2;
+                }
             }
         }
         // d hc = W_oc^T d rawc, through the ReLU
@@ -1262,6 +1306,12 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     unsigned wA[24], wB[24], xA[24], xB[24];
     unsigned d3h[8], d3m[8], d3l[8], d2h[8], d2m[8], d2l[8], d1h[8], d1m[8], d1l[8], dF3[24], dF1[24];
     const auto nothing = [](int) {};
+    // d(projection) += d(slot) * cos * pi * 2^f, formed behind matrix instruction i of a weight-gradient chain (v is tied behind it).  TD: the
+    // sum is tied where it is formed - untied it is placed at its use, in the B_layer unit, which has no matrix instruction to hide it
+    const auto dproj_add = [&](int d, float v, float c) {
+        if constexpr (TD) { const float sum = dproj[d] + v * c; dproj[d] = wv::after(sum, sum); }
+        else dproj[d] += v * c;
+    };
 #define VS_FIN(KIND, K, QI, STG, OW, OB, BLK, NC)                                                                             \
     [&](int i) {                                                                                                              \
         if (i == 0) fin_chunk<KIND, K, MULTI>(0, fs, qacc[QI], STG, OW, OB, BLK, NC, wave, p31, hi);                          \
@@ -1293,7 +1343,7 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     mm_dw_il<false, B6>(acc, accb, dF, xB, [&](int i) {
         if (i < 4) {
 #pragma unroll
-            for (int r = 4 * i; r < 4 * i + 4; ++r) dproj[r >> 1] += wv::after(acc2[r], acc[0]) * cfac[r >> 1][4 + (r & 1)];     // slot R = r: direction r >> 1, octave 4 + (r & 1)
+            for (int r = 4 * i; r < 4 * i + 4; ++r) dproj_add(r >> 1, wv::after(acc2[r], acc[0]), cfac[r >> 1][4 + (r & 1)]);     // slot R = r: direction r >> 1, octave 4 + (r & 1)
         }
     });
     VS_BWD_BARRIER();
@@ -1309,7 +1359,7 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     mm_dw_il<false, B6>(acc, accb, dF, xA, [&](int i) {
         if (i < 3) {
 #pragma unroll
-            for (int r = 2 * i; r < 2 * i + 2; ++r) dproj[8 + (r >> 1)] += wv::after(acc2[r], acc[0]) * cfac[8 + (r >> 1)][4 + (r & 1)];   // slots 16..21: directions 8..10
+            for (int r = 2 * i; r < 2 * i + 2; ++r) dproj_add(8 + (r >> 1), wv::after(acc2[r], acc[0]), cfac[8 + (r >> 1)][4 + (r & 1)]);   // slots 16..21: directions 8..10
         }
     });
     toF_mm3<4, NPB>(dF, d4h, d4m, d4l, SEL);                                 // F(d4) (F(d hc) was the delta of units 0..2)
@@ -1327,12 +1377,9 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     zero_acc(accb);
     mm_dw_il<true, B6>(acc, accb, dF, xB, [&](int i) {
 #pragma unroll
-        for (int j = i * 8 / NDB; j < (i + 1) * 8 / NDB; ++j) mask_split_pair<NPB>(j, acc2, h3h, d3h, d3m, d3l, i < NDW ? acc[0] : accb[0]);
+        for (int j = i * 8 / NDB; j < (i + 1) * 8 / NDB; ++j) mask_split_pair<NPB, TC>(j, acc2, h3h, d3h, d3m, d3l, i < NDW ? acc[0] : accb[0]);
     });
-    if (p31 == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Gv[I::B_M2 + phi(r, hi)] += accb[r];
-    }
+    bias_sums_put<ZC>(Gv + I::B_M2, accb, p31, hi);
     toF_mm3<4, NPB>(dF3, d3h, d3m, d3l, SEL);                                // F(d3): kept for the three first-group blocks
     VS_BWD_BARRIER();
     VS_MARK(8);
@@ -1364,12 +1411,9 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
     zero_acc(accb);
     mm_dw_il<true, B6>(acc, accb, dF, xB, [&](int i) {
 #pragma unroll
-        for (int j = i * 8 / NDB; j < (i + 1) * 8 / NDB; ++j) mask_split_pair<NPB>(j, acc2, h1h, d1h, d1m, d1l, i < NDW ? acc[0] : accb[0]);
+        for (int j = i * 8 / NDB; j < (i + 1) * 8 / NDB; ++j) mask_split_pair<NPB, TC>(j, acc2, h1h, d1h, d1m, d1l, i < NDW ? acc[0] : accb[0]);
     });
-    if (p31 == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Gv[I::B_M1 + phi(r, hi)] += accb[r];
-    }
+    bias_sums_put<ZC>(Gv + I::B_M1, accb, p31, hi);
     toF_mm3<4, NPB>(dF1, d1h, d1m, d1l, SEL);                                // F(d1): kept for the three in_layer blocks
     VS_BWD_BARRIER();
     VS_MARK(10);
@@ -1412,7 +1456,7 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 #pragma unroll
                 for (int r = 4 * i; r < 4 * i + 4; ++r) {
                     const int R = 16 * blk + r;
-                    if (R < 44) dproj[R >> 2] += wv::after(de[r], acc[0]) * cfac[R >> 2][R & 3];
+                    if (R < 44) dproj_add(R >> 2, wv::after(de[r], acc[0]), cfac[R >> 2][R & 3]);
                 }
             }
         });
@@ -1454,7 +1498,10 @@ __device__ __forceinline__ void step_main_s32_body(const StepArgs& a) {
 #pragma unroll
             for (int sl = 0; sl < 3; ++sl) {
                 const int v = 16 * sl + (lane & 15);
-                if (v < 33) Gv[I::G_PEB + 36 * hi + v] += keep[sl];
+                if (v < 33) {
+                    if constexpr (ZC) Gv[I::G_PEB + 36 * hi + v] = 0.0f + keep[sl];
+                    else Gv[I::G_PEB + 36 * hi + v] += keep[sl];
+                }
             }
         }
         VS_BWD_BARRIER();
@@ -1524,6 +1571,11 @@ __global__ __launch_bounds__(kWG, 1) void step_main_s32(const StepArgs a) {
 template <bool MULTI, bool W3, bool B6>
 __global__ __launch_bounds__(kWG, 1) void step_main_s32_of(const StepArgs a) {
     step_main_s32_body<true, MULTI, false, W3, B6, false, false, true>(a);
+}
+// the former backward (OB): training instantiations of the measurement build, with and without phase stamps
+template <bool MULTI, bool STAMPS, bool W3, bool B6>
+__global__ __launch_bounds__(kWG, 1) void step_main_s32_ob(const StepArgs a) {
+    step_main_s32_body<true, MULTI, STAMPS, W3, B6, false, false, false, true>(a);
 }
 
 }  // namespace vk

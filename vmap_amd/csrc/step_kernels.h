@@ -100,6 +100,8 @@ struct StepArgs {
                                        // bit 1 = ... the instantiation with the former order of the global loads (tuning.ws_flags bit 4; training)
                                        // bit 2 = ... the instantiation with the former order of the front: every encoding plane split and cos * pi * 2^f formed
                                        // in front of the image barrier (tuning.ws_flags bit 5; training)
+                                       // bit 3 = ... the instantiation with the former backward: untied mid1 / mid2 chunks and d(projection) products,
+                                       // read-modify-write bias sums (tuning.ws_flags bit 6; training, with or without phase stamps)
 };
 
 // Sample point `smp` of ray `ray` of object `obj` in the object frame: read from the points tensor (train.py:272 batch_input_pcs),

@@ -118,7 +118,7 @@ inline int plan_family(const vmapstep_shape* sh, bool measurement_build, Family&
     // every further round re-reads and re-writes its 1.4 MB gradient row and the step becomes bound by that traffic - still ahead
     // of the exact-fp32 kernels (the reference's own iMAP batch, 4800 rays: 3.50 -> 2.38 ms, profiles/r04i_*)
     if (H == 256 && sh->samples <= 32 && (force == VMAPSTEP_KERNEL_AUTO || force == VMAPSTEP_KERNEL_WS1)) fam = kWs;
-    if (!measurement_build && split32(fam) && (tun.ws_flags & (8 | 16 | 32)))      // hidden 32, A/B forms of step_main_s32: the B_layer.weight gradient with one butterfly per value (bit 3), the former order of the global loads (bit 4), the former order of the front (bit 5)
+    if (!measurement_build && split32(fam) && (tun.ws_flags & (8 | 16 | 32 | 64)))      // hidden 32, A/B forms of step_main_s32: the B_layer.weight gradient with one butterfly per value (bit 3), the former order of the global loads (bit 4), the former order of the front (bit 5), the former backward (bit 6)
         return fail(VMAPSTEP_ERR_UNSUPPORTED, "%s", kMeasurementOnly);
     if ((force == VMAPSTEP_KERNEL_WS1 || force == VMAPSTEP_KERNEL_WP) && !block_native_rows(fam))
         return fail(VMAPSTEP_ERR_UNSUPPORTED, "VMAPSTEP_KERNEL_WS1 / _WP: hidden 64 / 128 with at most 64 samples per ray (_WS1 also hidden 256 with at most 32)");
@@ -242,7 +242,7 @@ inline void fill_step_plan(vk::StepArgs& a, const vmapstep_shape* sh, const Plan
     a.wide = step_args_wide(pl.family);
     a.split = split32(pl.family) ? 1 : 0;
     a.bwd6 = pl.family == kS32Bwd6 ? 1 : 0;
-    a.ab_flags = split32(pl.family) ? ((tuning_of(sh).ws_flags & 8) ? 1 : 0) | ((tuning_of(sh).ws_flags & 16) ? 2 : 0) | ((tuning_of(sh).ws_flags & 32) ? 4 : 0) : 0;
+    a.ab_flags = split32(pl.family) ? ((tuning_of(sh).ws_flags & 8) ? 1 : 0) | ((tuning_of(sh).ws_flags & 16) ? 2 : 0) | ((tuning_of(sh).ws_flags & 32) ? 4 : 0) | ((tuning_of(sh).ws_flags & 64) ? 8 : 0) : 0;
 }
 // the workspace sections the kernels of pl.family read and write
 inline void fill_step_workspace(vk::StepArgs& a, const Plan& pl, char* ws) {
